@@ -19,6 +19,12 @@ forward, loss, backward, bucketed gradient all-reduce, grad-norm clip and
 fused AdamW update.  Rank 0 prints ONE JSON line.  Weak scaling: the per-GPU
 micro-batch is fixed (default 64 x 1024 tokens: at N = 8 that is GPT-2's own
 512-sequence global batch), the global batch is micro-batch × N.
+
+A plain run does only what that line needs: set up, warm up, time the K steps.
+``--dump-outputs DIR`` also writes what the last timed step computed (loss, updated
+parameters, gradients) as ``DIR/<name>.npy``.  ``--full`` adds everything else: the
+data-parallel step's phase-timed diagnostic step (``config.ddp_diag``) and the GEMM
+autotuner's measured table (``<--out-dir>/gemm_tuning_<model>.json``).
 """
 
 from __future__ import annotations
@@ -68,7 +74,18 @@ def parse_args(argv=None):
     ap.add_argument("--device", default=None, help="cpu: run the same harness on the CPU/gloo path (tests)")
     ap.add_argument("--ce-chunk", type=int, default=0,
                     help="GPT-2: LM head + loss over token chunks of this size (0: whole batch)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (its loss, the updated "
+                         "parameters, its gradients) as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the data-parallel step's phase-timed "
+                         "diagnostic step (ddp_diag) and the measured GEMM tuning table, written to --out-dir")
+    ap.add_argument("--out-dir", default="bench_out",
+                    help="where --full and --profile-steps write their files (created when needed)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_workers(args, argv):
@@ -175,9 +192,11 @@ def main(argv=None):
         rank_ms = [None] * world
         dist.all_gather_object(rank_ms, round((t1 - t0) * 1000 / max(args.steps, 1), 3))
     last_loss = float(loss)
-    # after the timed loop: one untimed, phase-timed eager step of the data-parallel path, so a first
-    # multi-GPU record says where its time went (exposed comm, collectives / bytes, schedule, spread)
-    diag = ddp_diagnostics(tr, world, rank_ms, sync) if tr.ddp is not None else None
+    if args.dump_outputs and tr.rank == 0:  # before anything below runs another step
+        dump_outputs(args.dump_outputs, tr, loss)
+    # --full, after the timed loop: one untimed, phase-timed eager step of the data-parallel path, so a
+    # first multi-GPU record says where its time went (exposed comm, collectives / bytes, schedule, spread)
+    diag = ddp_diagnostics(tr, world, rank_ms, sync) if (args.full and tr.ddp is not None) else None
 
     if args.profile_steps and tr.rank == 0:
         from torch.profiler import ProfilerActivity, profile
@@ -185,8 +204,8 @@ def main(argv=None):
             for i in range(args.profile_steps):
                 tr.step()
             sync()
-        os.makedirs("gpurun_out", exist_ok=True)
-        with open("gpurun_out/torch_profile.txt", "w") as f:
+        os.makedirs(args.out_dir, exist_ok=True)
+        with open(os.path.join(args.out_dir, "torch_profile.txt"), "w") as f:
             f.write(prof.key_averages().table(sort_by="cuda_time_total", row_limit=60))
 
     graphs = [tr._graph is not None]
@@ -235,15 +254,39 @@ def main(argv=None):
         },
     }
     if tr.rank == 0:
-        if dev.type == "cuda" and os.path.isdir("gpurun_out"):  # the measured per-shape GEMM configs (runtime autotuner)
-            os.makedirs("gpurun_out", exist_ok=True)
-            with open(f"gpurun_out/gemm_tuning_{args.model}.json", "w") as f:
+        if args.full and dev.type == "cuda":  # the measured per-shape GEMM configs (runtime autotuner)
+            os.makedirs(args.out_dir, exist_ok=True)
+            with open(os.path.join(args.out_dir, f"gemm_tuning_{args.model}.json"), "w") as f:
                 f.write(torch.ops.replicann.gemm_tuning_table())
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 4 * 2**20  # elements kept of each flat buffer larger than this (2 x 16 MiB as float32)
+
+
+def dump_outputs(path, tr, loss):
+    """``--dump-outputs``: what a caller of the timed step holds after the last timed step, as
+    float32 ``.npy`` files: ``loss`` (the step's return value), ``params`` (the parameters the step
+    updated, the flat buffer in layout order) and ``grads`` (the gradients it formed).  A buffer of
+    more than DUMP_SAMPLE elements is written as a fixed sample: the elements at DUMP_SAMPLE sorted
+    indices drawn once from a generator seeded with 0, the same for every run of the same model.
+    The seeds of the weights, the data and the device RNG streams are fixed, so two runs with the
+    same arguments start from identical inputs and their files compare element for element."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1), "params": tr.flat.data, "grads": tr.flat.grad}
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.detach().float().cpu().numpy())
 
 
 def ddp_diagnostics(tr, world, rank_ms, sync):

@@ -2,8 +2,8 @@
 autotuner measured for each BASELINE model's training step on an MI355X, loaded before the first
 step so every process and every box runs the same kernels for those shapes (the autotuner still
 times any shape a table does not cover).  Regenerate after a GEMM kernel change with
-``scripts/gen_tuning_tables.sh`` on a GPU box (``bench.py`` writes the measured table of its run
-to ``gpurun_out/gemm_tuning_<model>.json``).  ``REPLICANN_GEMM_TABLES=0`` skips loading."""
+``scripts/gen_tuning_tables.sh`` on a GPU box (``bench.py --full`` writes the measured table of its
+run to ``bench_out/gemm_tuning_<model>.json``).  ``REPLICANN_GEMM_TABLES=0`` skips loading."""
 
 from __future__ import annotations
 

@@ -1,13 +1,14 @@
 """Record the REFERENCE's outputs for the GPU parity tests.
 
-Runs the reference implementation itself — /root/reference/src/replicann, imported read-only —
-in fp32 on the CPU with deterministic weights/inputs (tests/refgen.py) and saves its forward
-outputs, return_kv tensors and the input gradients of an eval-mode backward to
-tests/fixtures/ref_gpu_parity.pt (tensors only, loaded with weights_only=True).  The GPU box has
-no /root/reference, so tests/test_reference_parity_gpu.py compares the native bf16 GPU path
-against these recorded reference results.
+Runs the reference implementation itself — its ``replicann`` package, imported read-only from
+REFERENCE_SRC — in fp32 on the CPU with deterministic weights/inputs (tests/refgen.py) and saves
+its forward outputs, return_kv tensors and the input gradients of an eval-mode backward to
+tests/golden/ref_gpu_parity.NN.pt (shards under 1 MiB, tensors only, loaded with
+weights_only=True: refgen.save_sharded / load_sharded).  A GPU box has no copy of the reference,
+so tests/test_reference_parity_gpu.py compares the native bf16 GPU path against these recorded
+reference results.
 
-    python scripts/gen_reference_fixtures.py
+    python scripts/gen_reference_fixtures.py REFERENCE_SRC [--io-floors]
 """
 
 import importlib
@@ -21,12 +22,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import refgen  # noqa: E402
 
 
-def load_reference():
-    sys.path.insert(0, "/root/reference/src")
+def load_reference(src):
+    sys.path.insert(0, src)
     for k in [k for k in sys.modules if k == "replicann" or k.startswith("replicann.")]:
         del sys.modules[k]
     tr = importlib.import_module("replicann.arch.transformer")
-    sys.path.remove("/root/reference/src")
+    sys.path.remove(src)
     return tr
 
 
@@ -38,8 +39,12 @@ def fwd_bwd(mod, *inputs, gseed, **kw):
     return y.detach(), [t.grad.detach() for t in ins]
 
 
-def main():
-    tr = load_reference()
+def _mib(paths):
+    return sum(os.path.getsize(p) for p in paths) / 2**20
+
+
+def main(src):
+    tr = load_reference(src)
     fx = {}
     for i, (name, cls, H, E, T, kw) in enumerate(refgen.CASES):
         torch.manual_seed(0)
@@ -61,14 +66,11 @@ def main():
     _, k, v = enc(src, return_kv=True)
     y, (gt, gk, gv) = fwd_bwd(dec, tgt, k.detach(), v.detach(), gseed=504)
     fx[name] = {"y": y.half(), "g_tgt": gt.half(), "g_k": gk.half(), "g_v": gv.half()}
-    os.makedirs(os.path.join(ROOT, "tests", "fixtures"), exist_ok=True)
-    out = os.path.join(ROOT, "tests", "fixtures", "ref_gpu_parity.pt")
-    torch.save(fx, out)
-    print(f"wrote {out} ({os.path.getsize(out) / 2**20:.1f} MiB), cases: {sorted(fx)}")
+    out = refgen.save_sharded(fx, "ref_gpu_parity")
+    print(f"wrote {len(out)} shards of ref_gpu_parity ({_mib(out):.1f} MiB), cases: {sorted(fx)}")
     gx = grad_fixtures(tr)
-    out = os.path.join(ROOT, "tests", "fixtures", "ref_gpu_grads.pt")
-    torch.save(gx, out)
-    print(f"wrote {out} ({os.path.getsize(out) / 2**20:.1f} MiB), cases: {sorted(gx)}")
+    out = refgen.save_sharded(gx, "ref_gpu_grads")
+    print(f"wrote {len(out)} shards of ref_gpu_grads ({_mib(out):.1f} MiB), cases: {sorted(gx)}")
     write_io_floors(tr)
 
 
@@ -153,7 +155,9 @@ def grad_fixtures(tr):
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] == ["--io-floors"]:  # only the small JSON (the .pt fixtures stay byte for byte)
-        write_io_floors(load_reference())
+    if len(sys.argv) < 2 or sys.argv[2:] not in ([], ["--io-floors"]):
+        sys.exit(__doc__)
+    if sys.argv[2:] == ["--io-floors"]:  # only the small JSON (the .pt shards stay byte for byte)
+        write_io_floors(load_reference(sys.argv[1]))
     else:
-        main()
+        main(sys.argv[1])

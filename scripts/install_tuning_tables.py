@@ -1,4 +1,4 @@
-"""Copy the tables measured by scripts/gen_tuning_tables.sh (gpurun_out/gemm_tuning_<model>.json)
+"""Copy the tables measured by scripts/gen_tuning_tables.sh (bench_out/gemm_tuning_<model>.json)
 into replicann_amd/tuning/gemm_<model>.json, sorted and one entry per line (reviewable diffs)."""
 
 import json
@@ -14,7 +14,7 @@ MODELS = ["gpt2-small", "gpt2-medium", "gpt2-medium-fp8", "vit-b16", "resnet18"]
 def main():
     n = 0
     for m in MODELS:
-        src = ROOT / "gpurun_out" / f"gemm_tuning_{m}.json"
+        src = ROOT / "bench_out" / f"gemm_tuning_{m}.json"
         if not src.exists():
             print(f"missing {src}", file=sys.stderr)
             continue

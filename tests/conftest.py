@@ -27,11 +27,12 @@ def pytest_collection_modifyitems(config, items):
 
 
 @pytest.fixture(scope="session")
-def ref():
-    """The reference package, imported read-only from /root/reference/src
-    (test-only; never vendored).  Skips when absent."""
-    if not REF_SRC.exists():
-        pytest.skip("reference not mounted")
+def ref_or_none():
+    """The reference package, imported read-only (test-only; never vendored) where a copy is
+    mounted and readable, else None.  The suite's own record of the reference is tests/golden/,
+    so no test needs the copy."""
+    if not (os.path.isdir(REF_SRC) and os.access(REF_SRC, os.R_OK | os.X_OK)):  # absent, or another user's
+        return None
     saved = {k: v for k, v in sys.modules.items() if k == "replicann" or k.startswith("replicann.")}
     for k in saved:
         del sys.modules[k]

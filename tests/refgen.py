@@ -1,6 +1,10 @@
 """Deterministic weights / inputs shared by scripts/gen_reference_fixtures.py (which runs the
-reference's own code from /root/reference/src on the CPU, fp32) and tests/test_reference_parity_gpu.py
-(which runs the native bf16 GPU path on the GPU box, where the reference is not mounted)."""
+reference's own code on the CPU, fp32) and tests/test_reference_parity_gpu.py (which runs the native
+bf16 GPU path on a GPU box, where there is no copy of the reference), and the sharded store of the
+recorded results under tests/golden/."""
+
+import glob
+import os
 
 import torch
 
@@ -51,6 +55,58 @@ GRAD_CASES = [  # name, block, n_heads, E, T, extra ctor kwargs
     ("gdec_h4_e256", "TransformerDecoder", 4, 256, 80, {"context_size": 128}),
 ]
 GRAD_CROSS = ("gxdec_h4_e256", 4, 256, 64, 48)  # encoder (return_kv) -> cross decoder, both trained
+
+
+# The recorded reference results are kept as shards under tests/golden/<stem>.NN.pt, each well under
+# 1 MiB: a nested dict of tensors is flattened to "case/sub/key" paths, packed greedily, and put
+# together again on load (weights_only: tensors, strings, numbers, lists).
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+SHARD_BYTES = 768 * 1024
+
+
+def _flatten(obj, prefix=""):
+    for k, v in obj.items():
+        assert "/" not in k, k
+        if isinstance(v, dict):
+            yield from _flatten(v, f"{prefix}{k}/")
+        else:
+            yield f"{prefix}{k}", v
+
+
+def save_sharded(obj, stem):
+    """Write ``obj`` (nested dicts, leaves: tensors / lists) as tests/golden/<stem>.NN.pt shards;
+    earlier shards of that stem are replaced.  Returns the paths written."""
+    os.makedirs(GOLDEN, exist_ok=True)
+    for old in glob.glob(os.path.join(GOLDEN, f"{stem}.[0-9][0-9].pt")):
+        os.remove(old)
+    shards, size = [{}], 0
+    for path, v in _flatten(obj):
+        n = v.numel() * v.element_size() if isinstance(v, torch.Tensor) else 64 * len(v)
+        assert n <= SHARD_BYTES, (path, n)
+        if size + n > SHARD_BYTES:
+            shards.append({})
+            size = 0
+        shards[-1][path] = v.clone() if isinstance(v, torch.Tensor) else v  # a clone: no shared storage saved whole
+        size += n
+    paths = []
+    for i, s in enumerate(shards):
+        paths.append(os.path.join(GOLDEN, f"{stem}.{i:02d}.pt"))
+        torch.save(s, paths[-1])
+    return paths
+
+
+def load_sharded(stem):
+    paths = sorted(glob.glob(os.path.join(GOLDEN, f"{stem}.[0-9][0-9].pt")))
+    assert paths, f"no shards of {stem} under {GOLDEN}"
+    out = {}
+    for p in paths:
+        for path, v in torch.load(p, weights_only=True).items():
+            *dirs, leaf = path.split("/")
+            d = out
+            for k in dirs:
+                d = d.setdefault(k, {})
+            d[leaf] = v
+    return out
 
 
 def zero_dropout(module):

@@ -1,7 +1,12 @@
 """T1 reference parity: same signatures, state_dict layout and
-forward outputs as /root/reference/src/replicann (fp32, eval mode, CPU)."""
+forward outputs as the reference's ``replicann`` package (fp32, eval mode, CPU).
+
+The reference side is recorded, not imported: ``scripts/gen_reference_golden.py`` ran the
+reference's own code and stored its signatures, weights (its own init), seeded inputs and outputs
+in ``tests/golden/ref_cpu_parity.pt``, so these tests need nothing outside the repository."""
 
 import inspect
+import os
 
 import pytest
 import torch
@@ -10,82 +15,86 @@ import replicann_amd.arch.transformer as T
 import replicann_amd.nn.attention as A
 
 ATOL = 2e-5
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_cpu_parity.pt")
 
 
-def _copy(ref_mod, new_mod):
-    new_mod.load_state_dict(ref_mod.state_dict(), strict=True)
+@pytest.fixture(scope="module")
+def gold():
+    return torch.load(GOLD, weights_only=True)
+
+
+def _copy(ref_sd, new_mod):
+    new_mod.load_state_dict(ref_sd, strict=True)
 
 
 def _sig(f):
-    return [(p.name, p.kind, p.default) for p in inspect.signature(f).parameters.values()]
+    return [[p.name, int(p.kind), repr(p.default)] for p in inspect.signature(f).parameters.values()]
 
 
-def _same_keys(a, b):
-    sa, sb = a.state_dict(), b.state_dict()
+def _same_keys(sa, b):
+    sb = b.state_dict()
     assert list(sa.keys()) == list(sb.keys())
     for k in sa:
         assert sa[k].shape == sb[k].shape, k
         assert sa[k].dtype == sb[k].dtype, k
 
 
+def _close(a, b):
+    torch.testing.assert_close(a, b, atol=ATOL, rtol=1e-5)
+
+
 @pytest.mark.parametrize("name", ["SelfAttentionHead", "CrossAttentionHead", "MultiheadSelfAttention",
                                   "MultiheadCrossAttention"])
-def test_attention_signatures(ref, name):
-    r = getattr(ref.attention, name)
+def test_attention_signatures(gold, name):
+    r = gold["signatures"][name]
     n = getattr(A, name)
-    assert _sig(r.__init__) == _sig(n.__init__)
-    assert _sig(r.forward) == _sig(n.forward)
+    assert r["init"] == _sig(n.__init__)
+    assert r["forward"] == _sig(n.forward)
 
 
 @pytest.mark.parametrize("name", ["TransformerEncoder", "TransformerDecoder", "TransformerCrossDecoder"])
-def test_block_signatures(ref, name):
-    r = getattr(ref.transformer, name)
+def test_block_signatures(gold, name):
+    r = gold["signatures"][name]
     n = getattr(T, name)
-    assert _sig(r.__init__) == _sig(n.__init__)
-    assert _sig(r.forward) == _sig(n.forward)
+    assert r["init"] == _sig(n.__init__)
+    assert r["forward"] == _sig(n.forward)
 
 
 @pytest.mark.parametrize("H,E", [(2, 8), (3, 12), (4, 10)])
-def test_encoder_parity(ref, H, E):
-    torch.manual_seed(0)
-    r = ref.transformer.TransformerEncoder(H, E).eval()
+def test_encoder_parity(gold, H, E):
+    r = gold[f"encoder_h{H}_e{E}"]
     n = T.TransformerEncoder(H, E).eval()
-    _same_keys(r, n)
-    _copy(r, n)
-    x = torch.randn(3, 7, E)
-    torch.testing.assert_close(n(x), r(x), atol=ATOL, rtol=1e-5)
+    _same_keys(r["sd"], n)
+    _copy(r["sd"], n)
+    _close(n(r["x"]), r["y"])
+    assert ("kv_y" in r) == (E % H == 0)
     if E % H == 0:  # the reference's return_kv path crashes otherwise (z width != E)
-        yr, kr, vr = r(x, return_kv=True)
-        yn, kn, vn = n(x, return_kv=True)
-        for a, b in ((yn, yr), (kn, kr), (vn, vr)):
-            torch.testing.assert_close(a, b, atol=ATOL, rtol=1e-5)
+        yn, kn, vn = n(r["x"], return_kv=True)
+        for a, b in ((yn, r["kv_y"]), (kn, r["kv_k"]), (vn, r["kv_v"])):
+            _close(a, b)
     # unbatched and extra leading dims
-    x2 = torch.randn(5, E)
-    torch.testing.assert_close(n(x2), r(x2), atol=ATOL, rtol=1e-5)
-    x4 = torch.randn(2, 2, 5, E)
-    torch.testing.assert_close(n(x4), r(x4), atol=ATOL, rtol=1e-5)
+    assert r["x2"].shape == (5, E) and r["x4"].shape == (2, 2, 5, E)
+    _close(n(r["x2"]), r["y2"])
+    _close(n(r["x4"]), r["y4"])
 
 
-def test_encoder_bias_options(ref):
-    torch.manual_seed(1)
+def test_encoder_bias_options(gold):
+    r = gold["encoder_bias_options"]
     kw = dict(ffn_bias=False, ffn_hidden_size=20, head_bias=True, proj_bias=False, p_dropout=0.0)
-    r = ref.transformer.TransformerEncoder(2, 8, **kw).eval()
     n = T.TransformerEncoder(2, 8, **kw).eval()
-    _same_keys(r, n)
-    _copy(r, n)
-    x = torch.randn(2, 6, 8)
-    torch.testing.assert_close(n(x), r(x), atol=ATOL, rtol=1e-5)
+    _same_keys(r["sd"], n)
+    _copy(r["sd"], n)
+    _close(n(r["x"]), r["y"])
 
 
-def test_decoder_parity_noncausal_mask(ref):
-    torch.manual_seed(2)
-    r = ref.transformer.TransformerDecoder(2, 8, context_size=16).eval()
+def test_decoder_parity_noncausal_mask(gold):
+    r = gold["decoder"]
     n = T.TransformerDecoder(2, 8, context_size=16).eval()
-    _same_keys(r, n)
+    _same_keys(r["sd"], n)
     assert list(n.state_dict())[0] == "_attn_mask"
-    _copy(r, n)
-    x = torch.randn(3, 9, 8)
-    torch.testing.assert_close(n(x), r(x), atol=ATOL, rtol=1e-5)
+    _copy(r["sd"], n)
+    x = r["x"]
+    _close(n(x), r["y"])
     # Q2: the additive 0/1 mask is NOT causal — a future token changes position 0
     x2 = x.clone()
     x2[:, -1] += 1.0
@@ -99,64 +108,57 @@ def test_decoder_bf16_buffer_accepted():
     assert y.dtype == torch.bfloat16 and torch.isfinite(y.float()).all()
 
 
-def test_cross_decoder_parity(ref):
-    torch.manual_seed(3)
-    re = ref.transformer.TransformerEncoder(2, 8).eval()
-    rd = ref.transformer.TransformerCrossDecoder(2, 8, context_size=12).eval()
+def test_cross_decoder_parity(gold):
+    r = gold["cross_decoder"]
     ne = T.TransformerEncoder(2, 8).eval()
     nd = T.TransformerCrossDecoder(2, 8, context_size=12).eval()
-    _same_keys(rd, nd)
-    _copy(re, ne)
-    _copy(rd, nd)
-    src, tgt = torch.randn(2, 10, 8), torch.randn(2, 6, 8)
-    _, kr, vr = re(src, return_kv=True)
-    _, kn, vn = ne(src, return_kv=True)
-    torch.testing.assert_close(nd(tgt, kn, vn), rd(tgt, kr, vr), atol=ATOL, rtol=1e-5)
+    _same_keys(r["dec_sd"], nd)
+    _copy(r["enc_sd"], ne)
+    _copy(r["dec_sd"], nd)
+    _, kn, vn = ne(r["src"], return_kv=True)
+    _close(kn, r["k"])
+    _close(vn, r["v"])
+    _close(nd(r["tgt"], kn, vn), r["y"])
 
 
-def test_heads_parity(ref):
-    torch.manual_seed(4)
-    for cls in ("SelfAttentionHead",):
-        r = getattr(ref.attention, cls)(8, 4).eval()
-        n = getattr(A, cls)(8, 4).eval()
-        _same_keys(r, n)
-        _copy(r, n)
-        x = torch.randn(2, 5, 8)
-        torch.testing.assert_close(n(x), r(x), atol=ATOL, rtol=1e-5)
-        zr, kr, vr = r(x, None, True)
-        zn, kn, vn = n(x, None, True)
-        torch.testing.assert_close(zn, zr, atol=ATOL, rtol=1e-5)
-        torch.testing.assert_close(kn, kr, atol=ATOL, rtol=1e-5)
-        assert n.embeddings_size == r.embeddings_size and n.head_size == r.head_size
-    r = ref.attention.CrossAttentionHead(8, 4).eval()
+def test_heads_parity(gold):
+    r = gold["self_head"]
+    n = A.SelfAttentionHead(8, 4).eval()
+    _same_keys(r["sd"], n)
+    _copy(r["sd"], n)
+    x = r["x"]
+    _close(n(x), r["y"])
+    zn, kn, vn = n(x, None, True)
+    _close(zn, r["kv_z"])
+    _close(kn, r["kv_k"])
+    _close(vn, r["kv_v"])
+    assert n.embeddings_size == r["embeddings_size"] and n.head_size == r["head_size"]
+    r = gold["cross_head"]
     n = A.CrossAttentionHead(8, 4).eval()
-    _copy(r, n)
-    x, k, v = torch.randn(2, 5, 8), torch.randn(2, 7, 4), torch.randn(2, 7, 4)
-    torch.testing.assert_close(n(x, k, v), r(x, k, v), atol=ATOL, rtol=1e-5)
+    _copy(r["sd"], n)
+    _close(n(r["x"], r["k"], r["v"]), r["y"])
 
 
-def test_masks(ref):
-    torch.manual_seed(5)
-    r = ref.attention.MultiheadSelfAttention(2, 4, 8).eval()
+def test_masks(gold):
+    r = gold["masks"]
     n = A.MultiheadSelfAttention(2, 4, 8).eval()
-    _copy(r, n)
-    x = torch.randn(2, 6, 8)
-    bmask = torch.triu(torch.ones(6, 6, dtype=torch.bool), 1)
-    torch.testing.assert_close(n(x, mask=bmask), r(x, mask=bmask), atol=ATOL, rtol=1e-5)
-    fmask = torch.randn(2, 6, 6)
-    torch.testing.assert_close(n(x, mask=fmask), r(x, mask=fmask), atol=ATOL, rtol=1e-5)
+    _copy(r["sd"], n)
+    x = r["x"]
+    assert r["bmask"].dtype == torch.bool and torch.equal(r["bmask"], torch.triu(torch.ones(6, 6, dtype=torch.bool), 1))
+    _close(n(x, mask=r["bmask"]), r["y_bmask"])
+    assert r["fmask"].shape == (2, 6, 6) and r["fmask"].dtype == torch.float32
+    _close(n(x, mask=r["fmask"]), r["y_fmask"])
     with pytest.raises(TypeError):
         n(x, mask=torch.ones(6, 6, dtype=torch.int32))
 
 
-def test_mhca_parity(ref):
-    torch.manual_seed(6)
-    r = ref.attention.MultiheadCrossAttention(2, 4, 8).eval()
+def test_mhca_parity(gold):
+    r = gold["mhca"]
     n = A.MultiheadCrossAttention(2, 4, 8).eval()
-    _same_keys(r, n)
-    _copy(r, n)
-    x, k, v = torch.randn(2, 5, 8), torch.randn(2, 7, 8), torch.randn(2, 7, 8)
-    torch.testing.assert_close(n(x, k, v), r(x, k, v), atol=ATOL, rtol=1e-5)
+    _same_keys(r["sd"], n)
+    _copy(r["sd"], n)
+    x, k, v = r["x"], r["k"], r["v"]
+    _close(n(x, k, v), r["y"])
     # Q6: return_kv works here (reference crashes)
     z, kk, vv = n(x, k, v, return_kv=True)
     assert z.shape == (2, 5, 8) and kk.shape == k.shape
@@ -169,13 +171,13 @@ def test_head_dropout_quirk():
     assert ps == [0.1, 0.1, 0.0, 0.0]
 
 
-def test_properties(ref):
-    r = ref.transformer.TransformerEncoder(3, 12)
+def test_properties(gold):
+    r = gold["properties"]
     n = T.TransformerEncoder(3, 12)
     for p in ("embedding_size", "head_size", "n_heads"):
-        assert getattr(n, p) == getattr(r, p)
-    assert n._ffn.hidden_size == r._ffn.hidden_size
-    assert n._attn.head_size == r._attn.head_size
+        assert getattr(n, p) == r[p]
+    assert n._ffn.hidden_size == r["ffn_hidden_size"]
+    assert n._attn.head_size == r["attn_head_size"]
 
 
 def test_train_mode_backward_runs():

@@ -1,9 +1,9 @@
 """GPU parity against the REFERENCE's own outputs.
 
-The reference blocks (/root/reference/src/replicann) were run in fp32 on the CPU by
+The reference blocks (its ``replicann`` package) were run in fp32 on the CPU by
 ``scripts/gen_reference_fixtures.py`` with deterministic weights and inputs (tests/refgen.py);
 their forward outputs, ``return_kv`` tensors and the input gradients of an eval-mode backward are
-recorded in tests/fixtures/ref_gpu_parity.pt (the GPU box has no /root/reference).  Here the SAME
+recorded in tests/golden/ref_gpu_parity.NN.pt (shards: ``refgen.load_sharded``).  Here the SAME
 weights, loaded with ``load_state_dict(strict=True)``, run through the native bf16 GPU path
 (fused QKV GEMM, fused attention kernel — head sizes 32, 64 and 128 — fused residual+LayerNorm,
 GEMM epilogues) and are compared as relative L2 errors at bf16 tolerance.
@@ -17,12 +17,10 @@ import torch
 import refgen
 import replicann_amd.arch.transformer as T
 
-FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures", "ref_gpu_parity.pt")
-
 
 @pytest.fixture(scope="module")
 def fx():
-    return torch.load(FIX, weights_only=True)
+    return refgen.load_sharded("ref_gpu_parity")  # tests/golden/ref_gpu_parity.NN.pt
 
 
 def rel(a, b):
@@ -79,25 +77,25 @@ def test_cross_decoder_gpu_vs_reference(cuda, fx):
         assert rel(a, b) < 3.5e-2
 
 
-def test_fixture_matches_live_reference(ref, fx):
-    """Where the reference IS mounted (this container, CPU): the recorded outputs are what the
-    reference code produces now."""
+def test_fixture_matches_live_reference(ref_or_none, fx):
+    """The recorded outputs are what the reference code produces now: re-run where a copy of the
+    reference is mounted, and everywhere through the native fp32 CPU path, which
+    tests/test_reference_parity.py holds to the reference's recorded outputs at 2e-5 (the
+    recording is fp16: 2^-11 per element, inside the 1e-3 asked here)."""
     i = 1
     name, cls, H, E, T_, kw = refgen.CASES[i]
-    torch.manual_seed(0)
-    m = getattr(ref.transformer, cls)(H, E, **kw).eval()
-    m.load_state_dict(refgen.det_state_dict(m, 100 + i), strict=True)
-    y = m(refgen.det_input((2, T_, E), 200 + i))
-    assert rel(y, fx[name]["y"]) < 1e-3
+    for impl in ([ref_or_none.transformer] if ref_or_none is not None else []) + [T]:
+        torch.manual_seed(0)
+        m = getattr(impl, cls)(H, E, **kw).eval()
+        m.load_state_dict(refgen.det_state_dict(m, 100 + i), strict=True)
+        y = m(refgen.det_input((2, T_, E), 200 + i))
+        assert rel(y, fx[name]["y"]) < 1e-3, impl.__name__
 
 
 # ---- parameter gradients (VERDICT r3 item 6): train mode, every dropout at p = 0 ----------------
-GFIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures", "ref_gpu_grads.pt")
-
-
 @pytest.fixture(scope="module")
 def gfx():
-    return torch.load(GFIX, weights_only=True)
+    return refgen.load_sharded("ref_gpu_grads")  # tests/golden/ref_gpu_grads.NN.pt
 
 
 def _train_block(cls, H, E, seed, dev, dtype, flat, **kw):
