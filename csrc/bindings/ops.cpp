@@ -75,8 +75,8 @@ int rn_gemm_skinny_kv(const void*, const void*, const void*, void*, int, int, in
 int rn_attn_fwd(const void*, const void*, const void*, void*, float*, const float*, int, const long*, int, int, int,
                 int, int, float, int, float, uint64_t, const uint64_t*, hipStream_t);
 int rn_attn_bwd(const void*, const void*, const void*, const void*, const void*, const float*, const float*, int,
-                void*, void*, void*, float*, float*, float*, const long*, int, int, int, int, int, float, int, float,
-                uint64_t, const uint64_t*, float*, void*, float*, int, float*, hipStream_t);
+                void*, void*, void*, float*, const long*, int, int, int, int, int, float, int, float, uint64_t,
+                const uint64_t*, float*, void*, float*, int, float*, hipStream_t);
 long rn_attn_q8_part_floats(int, int, int, int);
 void rn_colsum_f32(const float*, int, int, float*, void*, int, hipStream_t);
 int rn_colsum_ws(int);
@@ -799,10 +799,10 @@ std::tuple<Tensor, Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tens
     int rc = rn_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
                          bias && bias->defined() ? bias->data_ptr<float>() : nullptr, bias_b, s.data(), B, H, Tq, Tk, D,
                          (float)scale, causal, (float)p, (uint64_t)seed, seed_ptr(seed_buf), cur_stream());
-    TORCH_CHECK(rc == 0, "attention: unsupported shape D=", D, " Tk=", Tk);
+    TORCH_CHECK(rc == 0, "attention: unsupported shape or failed launch (", rc, ") D=", D, " Tk=", Tk);
     return {o, lse};
 }
-// q8 / q8st / q8_only: see AttnArgs (attention.hip); returns false (nothing launched) when the kernels
+// q8 / q8st / q8_only: see AttnArgs (attention_common.h); returns false (nothing launched) when the kernels
 // cannot emit e5m2 for this shape
 bool attn_bwd_impl(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
                    const Tensor& lse, const optional<Tensor>& bias, double scale, bool causal, double p, int64_t seed,
@@ -813,7 +813,6 @@ bool attn_bwd_impl(const Tensor& dout, const Tensor& q, const Tensor& k, const T
     std::vector<long> s;
     for (const Tensor* t : {&q, &k, &v, &o, &dout, &dq, &dk, &dv}) strides_bth(*t, s);
     Tensor delta = at::empty({B, H, Tq}, q.options().dtype(at::kFloat));
-    Tensor dk32, dv32;  // (no scratch: the generic path's dK/dV kernel writes dk / dv directly)
     int bias_b = bias && bias->defined() ? bias->size(0) : 1;
     if (B * H * Tq == 0) return true;
     // packed-QKV bias gradient: per-64-row-block column partials from the kernels, then one reduction
@@ -829,12 +828,11 @@ bool attn_bwd_impl(const Tensor& dout, const Tensor& q, const Tensor& k, const T
     Tensor q8part = q8 ? at::empty({rn_attn_q8_part_floats(B, H, Tq, Tk)}, q.options().dtype(at::kFloat)) : Tensor();
     int rc = rn_attn_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
                          bias && bias->defined() ? bias->data_ptr<float>() : nullptr, bias_b, dq.data_ptr(), dk.data_ptr(),
-                         dv.data_ptr(), delta.data_ptr<float>(), dk32.defined() ? dk32.data_ptr<float>() : nullptr,
-                         dv32.defined() ? dv32.data_ptr<float>() : nullptr, s.data(), B, H, Tq, Tk, D, (float)scale,
-                         causal, (float)p, (uint64_t)seed, seed_ptr(seed_buf), want_bg ? bsum.data_ptr<float>() : nullptr,
-                         q8, q8st, q8_only ? 1 : 0, q8 ? q8part.data_ptr<float>() : nullptr, cur_stream());
+                         dv.data_ptr(), delta.data_ptr<float>(), s.data(), B, H, Tq, Tk, D, (float)scale, causal, (float)p,
+                         (uint64_t)seed, seed_ptr(seed_buf), want_bg ? bsum.data_ptr<float>() : nullptr, q8, q8st,
+                         q8_only ? 1 : 0, q8 ? q8part.data_ptr<float>() : nullptr, cur_stream());
     if (rc == -3 && q8) return false;
-    TORCH_CHECK(rc == 0, "attention backward: unsupported shape D=", D);
+    TORCH_CHECK(rc == 0, "attention backward: unsupported shape or failed launch (", rc, ") D=", D);
     if (want_bg) {
         const int C = 3 * H * D;
         Tensor tmp = at::empty({rn_colsum_ws(C)}, q.options().dtype(at::kFloat));

@@ -57,9 +57,10 @@ if DEV:
 # Per-translation-unit extra flags.  The attention kernels run VALU-bound beside their MFMAs;
 # SLP vectorisation packs adjacent f32 adds/muls into v_pk_add/v_pk_mul_f32, which cost ~22-26
 # extra cycles each next to an MFMA (MI355X guide: 'price of one filler beside MFMAs').
-FILE_FLAGS = {
-    "attention": os.environ.get("REPLICANN_ATTN_FLAGS", "-fno-slp-vectorize").split(),
-}
+# (An explicit list of stems: attention_decode.hip is not VALU-bound beside MFMAs and keeps the defaults.)
+ATTN_UNITS = ["attention", "attention_fwd", "attention_mfma32", "attention_generic"] + [
+    f"attention_{fam}_d{d}" for fam in ("dq", "dkdv") for d in (32, 64, 128)]
+FILE_FLAGS = {stem: os.environ.get("REPLICANN_ATTN_FLAGS", "-fno-slp-vectorize").split() for stem in ATTN_UNITS}
 
 
 def _torch_paths():

@@ -1,4 +1,4 @@
-"""Fused scaled-dot-product attention (csrc/kernels/attention.hip).
+"""Fused scaled-dot-product attention (csrc/kernels/attention.hip and the attention_*.hip kernel units).
 
 Replaces the reference's per-head Python loop
 (``src/replicann/nn/attention.py:28-50`` — ``q@kᵀ*scale`` → mask → softmax →
@@ -32,8 +32,8 @@ MFMA_HEAD_DIMS = (32, 64, 128)
 
 
 def attention_is_mfma(head_dim: int) -> bool:
-    """True if ``head_dim`` runs on the MFMA flash kernels (deterministic, no atomics); other head
-    sizes take the generic per-query-row kernels (fp32 atomics in the backward)."""
+    """True if ``head_dim`` runs on the MFMA flash kernels; other head sizes take the generic scalar
+    kernels (dQ per query row, then dK/dV per key row).  Both are deterministic: no atomics."""
     return int(head_dim) in MFMA_HEAD_DIMS
 
 

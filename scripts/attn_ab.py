@@ -1,7 +1,7 @@
 """Time the production attention kernels (forward, backward) on GPT-2-small shapes (H=12, T=1024,
 D=64, causal by default), batch from argv (default 64), random data, several rounds.
 
-    python scripts/attn_ab.py [B] [--rounds 3] [--D 64] [--T 1024] [--noncausal]
+    python scripts/attn_ab.py [B] [--rounds 3] [--D 64] [--T 1024] [--noncausal] [--dropout P]
 
 Kernel revisions are compared by building each into its own library (REPLICANN_BUILD_OUT) and
 running this script once per library (REPLICANN_SO=...): the outputs' checksums are printed so two
@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--T", type=int, default=1024, help="sequence length (ViT-B/16: 197, non-causal)")
     ap.add_argument("--bias-grad", action="store_true",
                     help="the packed QKV projection's bias gradient from the backward kernels (producer_bias)")
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="attention dropout (D = 64: the single-loop forward and the one-group backward kernels)")
     a = ap.parse_args()
     B, T, D = a.B, a.T, a.D
     H = 768 // D
@@ -54,7 +56,8 @@ def main():
         flat = FlatParams(mod)
         flat.zero_grad()
         pb = mod.pb
-    fwd = lambda: ops.attention_packed(qkv, causal=not a.noncausal, producer_bias=pb)
+    fwd = lambda: ops.attention_packed(qkv, causal=not a.noncausal, producer_bias=pb, dropout_p=a.dropout,
+                                       training=a.dropout > 0)
     out = fwd()
     bwd = lambda: torch.autograd.grad(out, qkv, go, retain_graph=True)[0]
     res = {"fwd": [], "bwd": []}
@@ -67,6 +70,7 @@ def main():
         ms = min(lst)
         fl = fl_f if ps == "fwd" else 2.5 * fl_f
         print(json.dumps(dict(op=f"attn_{ps}", B=B, H=H, T=T, D=D, causal=not a.noncausal, bias_grad=a.bias_grad,
+                              dropout=a.dropout,
                               ms=round(ms, 4),
                               tflops=round(fl / ms / 1e9, 1), all_ms=[round(x, 4) for x in lst],
                               abs_sum=sums[ps])), flush=True)

@@ -482,6 +482,16 @@ def test_attention_d64_causal_offsets(cuda):
     _attn_check(1, 130, 2, 64, False, Tk=70)
 
 
+def test_attention_d64_noncausal_streaming(cuda):
+    """Non-causal D=64 with Tq or Tk above 256 (past the whole-head-resident kernels): the split-loop
+    forward attn_fwd64v2_k and the non-causal two-group dQ / dK-dV, against the fp32 reference — full
+    and ragged tiles, Tq != Tk either way."""
+    torch.manual_seed(71)
+    _attn_check(2, 320, 3, 64, False)
+    _attn_check(1, 130, 2, 64, False, Tk=300)
+    _attn_check(1, 300, 2, 64, False, Tk=70)
+
+
 def test_attention_bias_additive(cuda):
     torch.manual_seed(8)
     T = 96
