@@ -68,10 +68,10 @@ int rn_gemm(const void*, const void*, void*, const void*, const void*, void*, fl
             long, long, long, int, int, int, int, int, int, int, hipStream_t, float*);
 int rn_gemm_cfg_bm(int);
 long rn_gemm_colpart_rows(int, int);
-int rn_attn_decode(const void*, const void*, const void*, const float*, void*, int, int, int, int, const long*, float,
-                   hipStream_t);
+int rn_attn_decode(const void*, const void*, const void*, const float*, const void*, int, void*, int, int, int, int,
+                   const long*, float, hipStream_t);
 int rn_gemm_skinny_kv(const void*, const void*, const void*, void*, int, int, int, long, long, long, void*,
-                      const int64_t*, long, long, int, hipStream_t);
+                      const int64_t*, int, int, long, long, int, hipStream_t);
 int rn_attn_fwd(const void*, const void*, const void*, void*, float*, const float*, int, const long*, int, int, int,
                 int, int, float, int, float, uint64_t, const uint64_t*, hipStream_t);
 int rn_attn_bwd(const void*, const void*, const void*, const void*, const void*, const float*, const float*, int,
@@ -726,7 +726,8 @@ void strides_bth(const Tensor& t, std::vector<long>& s) {
     s.push_back(t.stride(0)); s.push_back(t.stride(1)); s.push_back(t.stride(2));
 }
 // decode-step QKV projection with the K|V cache append fused into the epilogue (gemm_skinny.hip):
-// x (M, K), w (N, K), kv (M, L, 2, H, D) contiguous cache, pos: 1 int64 device row index
+// x (M, K), w (N, K), kv (M, L, 2, H, D) contiguous cache, pos: int64 device row index, 1 element
+// (shared by the batch) or M (one per batch row); a position outside [0, L) appends nothing
 Tensor linear_kv(const Tensor& x, const Tensor& w, const optional<Tensor>& bias, const Tensor& kv, const Tensor& pos) {
     CHECK_CUDA(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(kv); GUARD(x);
     TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && w.dim() == 2 && w.stride(1) == 1, "linear_kv: 2-D row-major operands");
@@ -735,7 +736,10 @@ Tensor linear_kv(const Tensor& x, const Tensor& w, const optional<Tensor>& bias,
     TORCH_CHECK(kv.dim() == 5 && kv.is_contiguous() && kv.size(0) == M && kv.size(2) == 2, "linear_kv: kv must be (M, L, 2, H, D)");
     const int64_t kvw = kv.size(2) * kv.size(3) * kv.size(4);
     TORCH_CHECK(kvw <= N, "linear_kv: cache row wider than the projection");
-    TORCH_CHECK(pos.scalar_type() == at::kLong && pos.numel() == 1 && pos.is_cuda(), "linear_kv: pos must be 1 int64 on the device");
+    TORCH_CHECK(pos.scalar_type() == at::kLong && (pos.numel() == 1 || pos.numel() == M) && pos.is_contiguous() &&
+                    pos.is_cuda(),
+                "linear_kv: pos must be 1 or M contiguous int64 values on the device");
+    TORCH_CHECK(kv.size(1) >= 1 && kv.size(1) <= (int64_t)1 << 30,"linear_kv: cache length out of range");
     TORCH_CHECK(w.device() == x.device() && kv.device() == x.device() && pos.device() == x.device() &&
                     (!bias || !bias->defined() || bias->device() == x.device()),
                 "linear_kv: x, w, bias, kv and pos must be on one device");
@@ -743,14 +747,17 @@ Tensor linear_kv(const Tensor& x, const Tensor& w, const optional<Tensor>& bias,
     Tensor c = at::empty({M, N}, x.options());
     const int rc = rn_gemm_skinny_kv(x.data_ptr(), w.data_ptr(), optr(bias), c.data_ptr(), (int)M, (int)N, (int)K,
                                      x.stride(0), w.stride(0), c.stride(0), kv.data_ptr(), pos.data_ptr<int64_t>(),
-                                     kv.stride(0), kv.stride(1), (int)(N - kvw), cur_stream());
+                                     pos.numel() == 1 ? 0 : 1, (int)kv.size(1), kv.stride(0), kv.stride(1),
+                                     (int)(N - kvw), cur_stream());
     TORCH_CHECK(rc == 0, "linear_kv: unsupported shape M=", M, " K=", K, " (M <= 64, K % 8 == 0)");
     return c;
 }
 
 // one-query attention over a KV cache (decode step, attention_decode.hip): q (B, 1, H, 64), k / v
-// (B, Tk, H, 64) strided views, mask: Tk fp32 additive shared by the batch (or none)
-Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, double scale) {
+// (B, Tk, H, 64) strided views, mask: Tk fp32 additive shared by the batch (or none); lens (instead
+// of a mask): (B,) int32 / int64 key counts, batch row b attends to keys 0 .. lens[b]-1 only
+Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, double scale,
+                   const optional<Tensor>& lens) {
     CHECK_BF16(q); CHECK_BF16(k); CHECK_BF16(v); GUARD(q);
     TORCH_CHECK(q.dim() == 4 && q.size(1) == 1, "attn_decode: one query per (batch, head)");
     const int B = q.size(0), H = q.size(2), D = q.size(3), Tk = k.size(1);
@@ -767,6 +774,15 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const opti
         TORCH_CHECK(mask->scalar_type() == at::kFloat && mask->is_contiguous() && mask->numel() == Tk &&
                         mask->device() == q.device(),
                     "attn_decode: mask must be Tk contiguous fp32 values on q's device");
+    const bool has_lens = lens && lens->defined();
+    if (has_lens) {
+        TORCH_CHECK(!(mask && mask->defined()), "attn_decode: lens cannot be combined with a mask");
+        TORCH_CHECK(lens->dim() == 1 && lens->size(0) == B && lens->is_contiguous(),
+                    "attn_decode: lens must be a contiguous (B,) tensor, got ", lens->sizes());
+        TORCH_CHECK(lens->scalar_type() == at::kInt || lens->scalar_type() == at::kLong,
+                    "attn_decode: lens must be int32 or int64, got ", lens->scalar_type());
+        TORCH_CHECK(lens->device() == q.device(), "attn_decode: lens must be on q's device");
+    }
     Tensor o = at::empty({B, 1, H, D}, q.options());
     std::vector<long> s;
     std::vector<long> t;
@@ -775,7 +791,9 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const opti
     strides_bth(v, t); s.insert(s.end(), t.begin(), t.end()); t.clear();
     strides_bth(o, t); s.push_back(t[0]); s.push_back(t[2]);
     const int rc = rn_attn_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                  mask && mask->defined() ? mask->data_ptr<float>() : nullptr, o.data_ptr(), B, H, Tk, D,
+                                  mask && mask->defined() ? mask->data_ptr<float>() : nullptr,
+                                  has_lens ? lens->data_ptr() : nullptr,
+                                  has_lens && lens->scalar_type() == at::kLong ? 1 : 0, o.data_ptr(), B, H, Tk, D,
                                   s.data(), (float)scale, cur_stream());
     TORCH_CHECK(rc == 0, "attn_decode: unsupported shape D=", D, " Tk=", Tk, " (D == 64, Tk <= 1024)");
     return o;
@@ -1271,7 +1289,7 @@ TORCH_LIBRARY(replicann, m) {
     m.def("gemm(Tensor a, Tensor b, bool ta, bool tb, Tensor? bias, Tensor? residual, int act, Tensor? preact, "
           "Tensor? out, bool accumulate, int split_k, bool out_fp32, Tensor? alpha=None, int cfg=-1, "
           "Tensor(a!)? bias_grad=None) -> Tensor");
-    m.def("attn_decode(Tensor q, Tensor k, Tensor v, Tensor? mask, float scale) -> Tensor");
+    m.def("attn_decode(Tensor q, Tensor k, Tensor v, Tensor? mask, float scale, Tensor? lens=None) -> Tensor");
     m.def("linear_kv(Tensor x, Tensor w, Tensor? bias, Tensor(a!) kv, Tensor pos) -> Tensor");
     m.def("bias_act_grad(Tensor dy, Tensor? h, int act, bool want_bias, Tensor(a!)? db_accum=None) -> (Tensor, Tensor)");
     m.def("act_fwd(Tensor x, int kind) -> Tensor");

@@ -10,22 +10,38 @@
 // chunk, key group) = (t % 8, t / 8): 16-byte value loads, ≤ Tk / 32 independent iterations per
 // thread, the 32 key groups merged in LDS in a fixed order.  Deterministic, no atomics.
 // Tk <= 4 · 256 = 1024 keys (GPT-2's context).
+//
+// LENS variant (ragged batches, GPT2.generate(prompt_lens=...)): instead of the shared mask, batch row
+// b attends to keys 0 .. lens[b]-1 of its view (lens: B device integers, clamped to [0, Tk] here, so
+// no device value can index past the view).  Rows at or past lens[b] are neither loaded nor staged:
+// work and bytes follow the real length and unwritten cache rows may hold anything.  lens[b] == 0
+// gives a zero row.  Same indexing, same reduction order: with lens[b] == Tk it is the unmasked
+// kernel bit for bit.
 #include "common.h"
 
 namespace {
 
 constexpr int DEC_T = 256, DEC_KPT = 4;  // threads, keys per thread in the score phase
 
+// LENS = false: aux = the fp32 key mask (or null); LENS = true: aux = B lengths (int64 if lens64, else int32)
+template <bool LENS>
 __global__ void __launch_bounds__(DEC_T) attn_decode64_k(const bf16* __restrict__ q, const bf16* __restrict__ k,
-                                                         const bf16* __restrict__ v, const float* __restrict__ mask,
-                                                         bf16* __restrict__ o, int H, int Tk, long q_sb, long q_sh,
-                                                         long k_sb, long k_st, long k_sh, long v_sb, long v_st,
-                                                         long v_sh, long o_sb, long o_sh, float scale) {
+                                                         const bf16* __restrict__ v, const void* __restrict__ aux,
+                                                         int lens64, bf16* __restrict__ o, int H, int Tk_view,
+                                                         long q_sb, long q_sh, long k_sb, long k_st, long k_sh,
+                                                         long v_sb, long v_st, long v_sh, long o_sb, long o_sh,
+                                                         float scale) {
     __shared__ float p_s[DEC_T * DEC_KPT];
     __shared__ float red[DEC_T / 64];
     __shared__ float part[32][64];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const float* mask = LENS ? nullptr : static_cast<const float*>(aux);
+    int Tk = Tk_view;  // keys this row reads
+    if constexpr (LENS) {
+        const long n = lens64 ? static_cast<const int64_t*>(aux)[b] : (long)static_cast<const int*>(aux)[b];
+        Tk = (int)(n < 0 ? 0 : (n > Tk_view ? (long)Tk_view : n));
+    }
     const float sl2 = scale * 1.4426950408889634f;
     // q (64 elements) in every thread's registers
     float qf[64];
@@ -94,13 +110,21 @@ __global__ void __launch_bounds__(DEC_T) attn_decode64_k(const bf16* __restrict_
 }  // namespace
 
 // q, o: (B, 1, H, 64); k, v: (B, Tk, H, 64) with the given element strides (unit D stride);
-// mask: Tk fp32 additive (or null).  Returns -1 for shapes this kernel does not take.
-extern "C" int rn_attn_decode(const void* q, const void* k, const void* v, const float* mask, void* o, int B, int H,
-                              int Tk, int D, const long* s, float scale, hipStream_t st) {
-    if (D != 64 || Tk < 1 || Tk > DEC_T * DEC_KPT) return -1;
+// mask: Tk fp32 additive (or null); lens (with no mask): B per-row key counts, int64 if lens64 else
+// int32.  Returns -1 for shapes this kernel does not take.
+extern "C" int rn_attn_decode(const void* q, const void* k, const void* v, const float* mask, const void* lens,
+                              int lens64, void* o, int B, int H, int Tk, int D, const long* s, float scale,
+                              hipStream_t st) {
+    if (D != 64 || Tk < 1 || Tk > DEC_T * DEC_KPT || (mask && lens)) return -1;
     for (int i = 0; i < 8; ++i)
         if (s[i] % 8 != 0) return -1;  // 16-byte row loads
-    attn_decode64_k<<<B * H, DEC_T, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, mask, (bf16*)o, H, Tk, s[0],
-                                             s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], scale);
+    if (lens)
+        attn_decode64_k<true><<<B * H, DEC_T, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, lens, lens64,
+                                                       (bf16*)o, H, Tk, s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7],
+                                                       s[8], s[9], scale);
+    else
+        attn_decode64_k<false><<<B * H, DEC_T, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, mask, 0,
+                                                        (bf16*)o, H, Tk, s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7],
+                                                        s[8], s[9], scale);
     return 0;
 }

@@ -123,13 +123,16 @@ class Attention(nn.Module):
             buf = cache.kv[layer]
             qkv = ops.linear_kv_append(h, self.c_attn.weight, self.c_attn.bias, buf, cache.pos_t)
             q = qkv.view(B, T, 3, self.n_head, E // self.n_head)[:, :, 0]
-            a = ops.attention_decode(q, buf[:, :, 0], buf[:, :, 1], cache.mask).reshape(B, T, E)
+            a = (ops.attention_decode(q, buf[:, :, 0], buf[:, :, 1], lens=cache.lens) if cache.per_seq else
+                 ops.attention_decode(q, buf[:, :, 0], buf[:, :, 1], cache.mask)).reshape(B, T, E)
             return self.c_proj(a, residual=residual)
         qkv = self.c_attn(h).view(B, T, 3, self.n_head, E // self.n_head)
         if cache is not None:
             q = qkv[:, :, 0]
             k_all, v_all = cache.update(layer, qkv[:, :, 1:3])
-            if cache.device_pos:  # device-position mode: the key mask carries causality
+            if cache.per_seq:  # per-sequence mode: each row reads its own lens[b] keys
+                a = ops.attention_decode(q, k_all, v_all, lens=cache.lens).reshape(B, T, E)
+            elif cache.device_pos:  # device-position mode: the key mask carries causality
                 a = (ops.attention_decode(q, k_all, v_all, cache.mask) if T == 1 else
                      ops.attention(q, k_all, v_all, bias=cache.mask)).reshape(B, T, E)
             else:
@@ -183,22 +186,58 @@ class KVCache:
         self.pos_t = None
         self.mask = None
         self.device_pos = False
+        # per-sequence mode (ragged batches, GPT2.decode_step(lens=...)): device positions with one
+        # entry per batch row.  pos_t (B,) is each row's write row, lens = pos_t + 1 the key count its
+        # attention reads once this step's row is appended (no mask: rows past it are never read),
+        # active (B,) 0 / 1 the rows that advance (0: a finished row stays where it is)
+        self.per_seq = False
+        self.lens = None
+        self.active = None
+        self._seq = None  # the per-sequence tensors, kept across reset() for a captured step
 
     def to_device_position(self):
         """Switch to device-position mode at the current host position (the same pos_t / mask
         tensors are refilled on later calls, so a graph captured on them stays valid)."""
-        if self.pos_t is None:
+        if self.mask is None:  # first call (or after per-sequence mode, which has no mask)
             dev = self.kv[0].device
             self.pos_t = torch.empty(1, dtype=torch.long, device=dev)
             self.mask = torch.empty(1, 1, self.max_len, device=dev)
         self.pos_t.fill_(self.pos)
         self.mask.fill_(float("-inf"))
         self.mask[..., : self.pos] = 0.0
-        self.device_pos = True
+        self.device_pos, self.per_seq = True, False
+
+    def to_per_sequence(self, lens):
+        """Switch to per-sequence mode after a right-padded prefill: row b holds ``lens[b]`` (B,)
+        valid positions.  Whatever the prefill wrote at or past lens[b] is never read and is
+        overwritten as the row grows.  The same tensors are refilled on later calls (a graph captured
+        on them stays valid).  Works on the CPU as well.  The host ``pos`` becomes max(lens): an upper
+        bound of every row's position, which eager steps check against the cache length."""
+        dev = self.kv[0].device
+        lens = torch.as_tensor(lens, dtype=torch.long).reshape(-1)
+        self.pos = int(lens.max())
+        lens = lens.to(dev)
+        if self._seq is None or self._seq[0].shape != lens.shape:
+            self._seq = tuple(torch.empty_like(lens) for _ in range(3))
+        self.pos_t, self.lens, self.active = self._seq
+        self.pos_t.copy_(lens)
+        torch.add(lens, 1, out=self.lens)
+        self.active.fill_(1)
+        self.mask = None
+        self.device_pos = self.per_seq = True
+
+    def step(self):
+        """End of a one-token device-position step: advance the position(s), once per step."""
+        if self.per_seq:
+            self.pos_t.add_(self.active)
+            self.lens.add_(self.active)
+            self.pos += 1
+        else:
+            self.pos_t.add_(1)
 
     def reset(self):
         """Start a new sequence in the same buffers (host-position mode, position 0)."""
-        self.pos, self.device_pos = 0, False
+        self.pos, self.device_pos, self.per_seq = 0, False, False
 
     def update(self, layer, kv):
         """Append ``kv`` (B, T, 2, H, D) — the key / value slice of the packed QKV projection — at
@@ -207,7 +246,12 @@ class KVCache:
         device-position mode)."""
         if self.device_pos:
             buf = self.kv[layer]
-            buf.index_copy_(1, self.pos_t, kv)
+            if self.per_seq:  # each row at its own position
+                if kv.shape[1] != 1:
+                    raise ValueError("KV cache in per-sequence mode appends one token per step")
+                buf.scatter_(1, self.pos_t.view(-1, 1, 1, 1, 1).expand_as(kv), kv)
+            else:
+                buf.index_copy_(1, self.pos_t, kv)
             return buf[:, :, 0], buf[:, :, 1]
         B, T, _, H, D = kv.shape
         if self.pos + T > self.max_len:

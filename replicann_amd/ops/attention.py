@@ -200,16 +200,35 @@ def attention_packed(qkv, *, scale=None, causal=False, bias=None, mask=None, dro
     return attention_reference(q, k, v, scale, causal, bias, p, training)
 
 
-def attention_decode(q, k, v, mask=None, scale=None):
+def attention_decode(q, k, v, mask=None, scale=None, *, lens=None):
     """One new query per (batch, head) against a KV cache — q (B, 1, H, D), k / v (B, Tk, H, D) —
     with an additive key mask (Tk values shared by the batch, or None).  Inference only.  On the GPU
     at head size 64 one launch of the one-query kernel (csrc/kernels/attention_decode.hip: a workgroup
-    per (batch, head), no query tiling); otherwise the general attention."""
+    per (batch, head), no query tiling); otherwise the general attention.
+
+    ``lens`` (instead of ``mask``): (B,) int32 / int64 on q's device — batch row b attends to keys
+    0 .. lens[b]-1 only (values are clamped to [0, Tk]; a row of length 0 gives zeros).  The native
+    kernel reads no key / value row at or past lens[b]; the fallback turns ``lens`` into a
+    (B, 1, Tk) -inf bias for the general attention, which reads (and so needs finite) every row."""
     B, Tq, H, D = q.shape
     if scale is None:
         scale = D ** -0.5
     Tk = k.shape[1]
-    if _ext.use_native(q) and Tq == 1 and D == 64 and Tk <= 1024 and not torch.is_grad_enabled():
+    native = _ext.use_native(q) and Tq == 1 and D == 64 and Tk <= 1024 and not torch.is_grad_enabled()
+    if lens is not None:
+        if mask is not None:
+            raise ValueError("attention_decode: lens cannot be combined with mask")
+        if lens.shape != (B,) or lens.dtype not in (torch.int32, torch.int64) or lens.device != q.device:
+            raise ValueError(f"attention_decode: lens must be ({B},) int32 / int64 on {q.device}, got "
+                             f"{tuple(lens.shape)} {lens.dtype} on {lens.device}")
+        if native:
+            return _ext.ops().attn_decode(q, k, v, None, float(scale), lens.contiguous())
+        open_ = torch.arange(Tk, device=q.device).view(1, 1, Tk) < lens.view(B, 1, 1)
+        bias = torch.zeros(B, 1, Tk, device=q.device).masked_fill_(~open_, float("-inf"))
+        empty = (lens <= 0).view(B, 1, 1, 1)  # no key at all: zeros, not the softmax of an all -inf row
+        bias = bias.masked_fill(empty.view(B, 1, 1), 0.0)
+        return attention(q, k, v, scale=scale, bias=bias.expand(B, Tq, Tk)).masked_fill(empty, 0.0)
+    if native:
         m = mask.reshape(-1) if mask is not None else None
         if m is None or (m.numel() == Tk and m.dtype == torch.float32 and m.is_contiguous()):
             return _ext.ops().attn_decode(q, k, v, m, float(scale))

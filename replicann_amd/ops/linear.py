@@ -260,15 +260,28 @@ def linear(x, weight, bias=None, act=None, residual=None, fp8=None):
 def linear_kv_append(x, weight, bias, kv, pos):
     """Decode-step QKV projection: y = x·weightᵀ + bias for one new token per batch row (x (B, 1, K)),
     and y's last 2·H·D columns (keys, values) written into the KV cache buffer ``kv`` (B, L, 2, H, D)
-    at the device-side row ``pos`` (1 int64).  Inference only.  On the GPU one launch: the append
-    is part of the skinny GEMM's epilogue (``torch.ops.replicann.linear_kv``)."""
+    at the device-side row ``pos`` (int64): 1 element = one row shared by the batch, B elements = row
+    ``pos[b]`` for batch row b (a position outside [0, L) appends nothing).  Inference only.  On the
+    GPU one launch: the append is part of the skinny GEMM's epilogue (``torch.ops.replicann.linear_kv``)."""
     B = x.shape[0]
+    if pos.numel() not in (1, B):
+        raise ValueError(f"linear_kv_append: pos must have 1 or {B} elements, got {pos.numel()}")
     if (_ext.use_native(x) and x.dim() == 3 and x.shape[1] == 1 and B <= 64 and not torch.is_grad_enabled()
             and kv.is_contiguous()):
-        return _ext.ops().linear_kv(x.reshape(B, -1).contiguous(), weight, bias, kv, pos).view(B, 1, -1)
+        return _ext.ops().linear_kv(x.reshape(B, -1).contiguous(), weight, bias, kv,
+                                    pos.reshape(-1).contiguous()).view(B, 1, -1)
     y = linear(x, weight, bias)
     w = kv[0, 0].numel()
-    kv.index_copy_(1, pos, y[..., -w:].reshape(B, y.shape[1], *kv.shape[2:]))
+    new = y[..., -w:].reshape(B, y.shape[1], *kv.shape[2:])
+    if pos.numel() == 1:
+        kv.index_copy_(1, pos.reshape(1), new)
+        return y
+    # one row per batch row: a scatter along dim 1; a row whose position is out of range keeps the
+    # cache row it is pointed at instead (nothing appended, and no out-of-range index on the device)
+    L = kv.shape[1]
+    p = pos.reshape(B, 1, 1, 1, 1)
+    idx = p.clamp(0, L - 1).expand(B, 1, *kv.shape[2:])
+    kv.scatter_(1, idx, torch.where((p >= 0) & (p < L), new.to(kv.dtype), kv.gather(1, idx)))
     return y
 
 

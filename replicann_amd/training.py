@@ -484,11 +484,16 @@ def eval_main(argv=None):
 def generate_main(argv=None):
     """``python -m replicann generate``: sample continuations from a GPT-2 model — random init, or a
     checkpoint written by ``train(checkpoint=...)`` — with the KV cache and the hipGraph-replayed
-    decode step (``GPT2.generate``).  Prints one JSON line: the token ids, decode timing."""
+    decode step (``GPT2.generate``).  Prints one JSON line: the token ids, decode timing.  ``--prompt``
+    may be repeated (one sequence each, of any lengths) and ``--eos`` stops a sequence at that token:
+    the line then carries each sequence's generated tokens and total length."""
     ap = argparse.ArgumentParser(description="replicann generation entrypoint (GPT-2 models)")
     ap.add_argument("--model", default="gpt2-small")
     ap.add_argument("--checkpoint", default=None)
-    ap.add_argument("--prompt", default=None, help="comma-separated token ids (default: random ids)")
+    ap.add_argument("--prompt", action="append", default=None,
+                    help="comma-separated token ids (default: random ids); repeat for a batch of sequences")
+    ap.add_argument("--eos", type=int, default=None, help="token id that ends a sequence")
+    ap.add_argument("--pad", type=int, default=None, help="token id emitted after the end (default: --eos, else 0)")
     ap.add_argument("--prompt-len", type=int, default=16)
     ap.add_argument("--batch-size", type=int, default=1)
     ap.add_argument("--new", type=int, default=32)
@@ -512,11 +517,30 @@ def generate_main(argv=None):
         from .tuning import load_committed
         load_committed(a.model)
         model = model.to(torch.bfloat16)
-    if a.prompt:
-        ids = torch.tensor([[int(t) for t in a.prompt.split(",")]] * a.batch_size, dtype=torch.long)
+    gen = torch.Generator(device=dev).manual_seed(a.seed)
+    prompts = [[int(t) for t in p.split(",")] for p in a.prompt or []]
+    if len(prompts) > 1 or a.eos is not None:  # ragged batch and / or stopping
+        if not prompts:
+            prompts = torch.randint(0, model.config.vocab_size, (a.batch_size, a.prompt_len)).tolist()
+        elif len(prompts) == 1:
+            prompts = prompts * a.batch_size
+        t0 = time.perf_counter()
+        rows = model.generate_batch([torch.tensor(p, dtype=torch.long) for p in prompts], a.new,
+                                    temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, generator=gen,
+                                    eos_token_id=a.eos, pad_token_id=a.pad)
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        dt = time.perf_counter() - t0
+        new = [r[len(p):].tolist() for r, p in zip(rows, prompts)]
+        res = {"model": a.model, "tokens": new, "prompt_lens": [len(p) for p in prompts],
+               "lengths": [int(r.numel()) for r in rows], "new_tokens": a.new, "seconds": round(dt, 4),
+               "tokens_per_s": round(sum(map(len, new)) / dt, 1)}
+        print(json.dumps(res))
+        return res
+    if prompts:
+        ids = torch.tensor(prompts * a.batch_size, dtype=torch.long)
     else:
         ids = torch.randint(0, model.config.vocab_size, (a.batch_size, a.prompt_len))
-    gen = torch.Generator(device=dev).manual_seed(a.seed)
     t0 = time.perf_counter()
     out = model.generate(ids.to(dev), a.new, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, generator=gen)
     if dev.type == "cuda":
