@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .decoding import KVCache  # noqa: F401  (its home; importable from here as before)
 
 
 class Linear(nn.Module):
@@ -118,26 +119,18 @@ class Attention(nn.Module):
         cache position and the queries attend to everything cached so far (causal, bottom-right
         aligned: query i of T new tokens sees keys ≤ pos + i)."""
         B, T, E = h.shape
-        if cache is not None and cache.device_pos and T == 1 and self.c_attn.fp8_state is None:
-            # captured decode step: the projection's epilogue appends this token's key / value row
-            buf = cache.kv[layer]
-            qkv = ops.linear_kv_append(h, self.c_attn.weight, self.c_attn.bias, buf, cache.pos_t)
-            q = qkv.view(B, T, 3, self.n_head, E // self.n_head)[:, :, 0]
-            a = (ops.attention_decode(q, buf[:, :, 0], buf[:, :, 1], lens=cache.lens) if cache.per_seq else
-                 ops.attention_decode(q, buf[:, :, 0], buf[:, :, 1], cache.mask)).reshape(B, T, E)
+        if cache is not None:
+            if cache.device_pos and T == 1 and self.c_attn.fp8_state is None:
+                # captured decode step: the projection's epilogue appends this token's key / value row
+                buf = cache.kv[layer]
+                qkv = ops.linear_kv_append(h, self.c_attn.weight, self.c_attn.bias, buf, cache.pos_t)
+                qkv, k, v = qkv.view(B, T, 3, self.n_head, E // self.n_head), buf[:, :, 0], buf[:, :, 1]
+            else:
+                qkv = self.c_attn(h).view(B, T, 3, self.n_head, E // self.n_head)
+                k, v = cache.update(layer, qkv[:, :, 1:3])
+            a = cache.attend(qkv[:, :, 0], k, v, self.causal).reshape(B, T, E)
             return self.c_proj(a, residual=residual)
         qkv = self.c_attn(h).view(B, T, 3, self.n_head, E // self.n_head)
-        if cache is not None:
-            q = qkv[:, :, 0]
-            k_all, v_all = cache.update(layer, qkv[:, :, 1:3])
-            if cache.per_seq:  # per-sequence mode: each row reads its own lens[b] keys
-                a = ops.attention_decode(q, k_all, v_all, lens=cache.lens).reshape(B, T, E)
-            elif cache.device_pos:  # device-position mode: the key mask carries causality
-                a = (ops.attention_decode(q, k_all, v_all, cache.mask) if T == 1 else
-                     ops.attention(q, k_all, v_all, bias=cache.mask)).reshape(B, T, E)
-            else:
-                a = ops.attention(q, k_all, v_all, causal=self.causal).reshape(B, T, E)
-            return self.c_proj(a, residual=residual)
         a = ops.attention_packed(qkv, causal=self.causal, dropout_p=self.attn_dropout,
                                  training=self.training,
                                  producer_bias=self.c_attn.bias,
@@ -170,103 +163,6 @@ class MLP(nn.Module):
         fp8 = (self.c_fc.fp8_state, self.c_proj.fp8_state) if self.c_fc.fp8 else None
         return ops.mlp(h, self.c_fc.weight, self.c_fc.bias, self.c_proj.weight, self.c_proj.bias, "gelu",
                        residual=residual, fp8=fp8)
-
-
-class KVCache:
-    """Per-layer key / value buffer for incremental decoding, (B, max_len, 2, H, D), allocated on
-    first use in the dtype / device of the keys (one HBM allocation per layer for the whole
-    generation; an append is one row copy, the attention reads strided key / value views)."""
-
-    def __init__(self, n_layer, max_len):
-        self.max_len, self.pos = max_len, 0
-        self.kv = [None] * n_layer
-        # device-position mode (a captured decode step, GPT2.generate(graph=True)): the write row is
-        # the 1-element device tensor pos_t and the attention reads the whole buffer under the additive
-        # key mask (1, 1, max_len): 0 for written rows, -inf past them — no host value per step
-        self.pos_t = None
-        self.mask = None
-        self.device_pos = False
-        # per-sequence mode (ragged batches, GPT2.decode_step(lens=...)): device positions with one
-        # entry per batch row.  pos_t (B,) is each row's write row, lens = pos_t + 1 the key count its
-        # attention reads once this step's row is appended (no mask: rows past it are never read),
-        # active (B,) 0 / 1 the rows that advance (0: a finished row stays where it is)
-        self.per_seq = False
-        self.lens = None
-        self.active = None
-        self._seq = None  # the per-sequence tensors, kept across reset() for a captured step
-
-    def to_device_position(self):
-        """Switch to device-position mode at the current host position (the same pos_t / mask
-        tensors are refilled on later calls, so a graph captured on them stays valid)."""
-        if self.mask is None:  # first call (or after per-sequence mode, which has no mask)
-            dev = self.kv[0].device
-            self.pos_t = torch.empty(1, dtype=torch.long, device=dev)
-            self.mask = torch.empty(1, 1, self.max_len, device=dev)
-        self.pos_t.fill_(self.pos)
-        self.mask.fill_(float("-inf"))
-        self.mask[..., : self.pos] = 0.0
-        self.device_pos, self.per_seq = True, False
-
-    def to_per_sequence(self, lens):
-        """Switch to per-sequence mode after a right-padded prefill: row b holds ``lens[b]`` (B,)
-        valid positions.  Whatever the prefill wrote at or past lens[b] is never read and is
-        overwritten as the row grows.  The same tensors are refilled on later calls (a graph captured
-        on them stays valid).  Works on the CPU as well.  The host ``pos`` becomes max(lens): an upper
-        bound of every row's position, which eager steps check against the cache length."""
-        dev = self.kv[0].device
-        lens = torch.as_tensor(lens, dtype=torch.long).reshape(-1)
-        self.pos = int(lens.max())
-        lens = lens.to(dev)
-        if self._seq is None or self._seq[0].shape != lens.shape:
-            self._seq = tuple(torch.empty_like(lens) for _ in range(3))
-        self.pos_t, self.lens, self.active = self._seq
-        self.pos_t.copy_(lens)
-        torch.add(lens, 1, out=self.lens)
-        self.active.fill_(1)
-        self.mask = None
-        self.device_pos = self.per_seq = True
-
-    def step(self):
-        """End of a one-token device-position step: advance the position(s), once per step."""
-        if self.per_seq:
-            self.pos_t.add_(self.active)
-            self.lens.add_(self.active)
-            self.pos += 1
-        else:
-            self.pos_t.add_(1)
-
-    def reset(self):
-        """Start a new sequence in the same buffers (host-position mode, position 0)."""
-        self.pos, self.device_pos, self.per_seq = 0, False, False
-
-    def update(self, layer, kv):
-        """Append ``kv`` (B, T, 2, H, D) — the key / value slice of the packed QKV projection — at
-        the cache position; returns the (key, value) views the attention reads.  K and V share one
-        (B, max_len, 2, H, D) buffer per layer, so an append is ONE copy (one index_copy_ in
-        device-position mode)."""
-        if self.device_pos:
-            buf = self.kv[layer]
-            if self.per_seq:  # each row at its own position
-                if kv.shape[1] != 1:
-                    raise ValueError("KV cache in per-sequence mode appends one token per step")
-                buf.scatter_(1, self.pos_t.view(-1, 1, 1, 1, 1).expand_as(kv), kv)
-            else:
-                buf.index_copy_(1, self.pos_t, kv)
-            return buf[:, :, 0], buf[:, :, 1]
-        B, T, _, H, D = kv.shape
-        if self.pos + T > self.max_len:
-            raise ValueError(f"KV cache full: {self.pos} + {T} > {self.max_len}")
-        if self.kv[layer] is None:
-            # zeroed, not empty: the device-position step reads the WHOLE buffer under the key mask, and
-            # a masked row still enters P·V as 0 · v — a NaN bit pattern in an unwritten row would
-            # turn that into NaN
-            self.kv[layer] = kv.new_zeros(B, self.max_len, 2, H, D)
-        buf = self.kv[layer]
-        buf[:, self.pos: self.pos + T].copy_(kv)
-        return buf[:, : self.pos + T, 0], buf[:, : self.pos + T, 1]
-
-    def advance(self, T):
-        self.pos += T
 
 
 class PreLNBlock(nn.Module):

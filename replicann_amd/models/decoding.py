@@ -1,0 +1,352 @@
+"""Incremental decoding: everything that is generation, not model.
+
+``KVCache`` owns everything that depends on its mode; ``generate`` is the sampling loop (uniform or
+ragged) over one ``_StepDriver``, which resolves the cache and runs the one-token step eagerly or as
+a hipGraph kept in the model's ``_GraphRegistry``.  The model (``models/gpt2.py``) keeps the pass.
+"""
+
+from __future__ import annotations
+
+import os
+import weakref
+
+import torch
+
+from .. import ops
+
+
+class KVCache:
+    """Per-layer key / value buffer for incremental decoding, (B, max_len, 2, H, D), allocated on
+    first use in the dtype / device of the keys (one HBM allocation per layer for the whole
+    generation; an append is one row copy, the attention reads strided key / value views).
+
+    ``mode`` says where the position lives and what the attention reads:
+      * ``"host"`` (a new or ``reset()`` cache; prefills): the host integer ``pos``; appends are slice
+        copies and the attention is the causal one over rows < pos + T.
+      * ``"device"`` (a captured step, ``generate(graph=True)``): the write row is the 1-element
+        device tensor ``pos_t`` and the attention reads the whole buffer under the additive key
+        ``mask`` (1, 1, max_len), 0 for written rows, -inf past them — no host value per step.
+      * ``"per_seq"`` (ragged batches, ``decode_step(lens=...)``): ``pos_t`` (B,) is each row's write
+        row, ``lens = pos_t + 1`` the key count its attention reads once this step's row is appended
+        (no mask: rows past it are never read), ``active`` (B,) 0 / 1 the rows that advance (0: a
+        finished row stays where it is).  ``pos`` is max over the rows: an upper bound.
+    A captured step reads the device tensors by address, so each is allocated once per cache and kept
+    through ``reset()`` and every mode change (the per-sequence triple: until the batch size changes)."""
+
+    def __init__(self, n_layer, max_len):
+        self.max_len, self.pos, self.mode = max_len, 0, "host"
+        self.kv = [None] * n_layer
+        self._pos1 = self.mask = None  # device mode
+        self._rows = self.lens = self.active = None  # per-sequence mode
+
+    device_pos = property(lambda self: self.mode != "host")
+    per_seq = property(lambda self: self.mode == "per_seq")
+
+    @property
+    def pos_t(self):
+        return self._rows if self.mode == "per_seq" else self._pos1 if self.mode == "device" else None
+
+    def to_device_position(self):
+        """Switch to device mode at the current host position."""
+        if self.mask is None:
+            dev = self.kv[0].device
+            self._pos1 = torch.empty(1, dtype=torch.long, device=dev)
+            self.mask = torch.empty(1, 1, self.max_len, device=dev)
+        self._pos1.fill_(self.pos)
+        self.mask.fill_(float("-inf"))
+        self.mask[..., : self.pos] = 0.0
+        self.mode = "device"
+
+    def to_per_sequence(self, lens):
+        """Switch to per-sequence mode after a right-padded prefill: row b holds ``lens[b]`` (B,)
+        valid positions; what the prefill wrote at or past lens[b] is never read and is overwritten as
+        the row grows.  The host ``pos`` becomes max(lens), which eager steps check against max_len."""
+        lens = torch.as_tensor(lens, dtype=torch.long).reshape(-1)
+        self.pos = int(lens.max())
+        lens = lens.to(self.kv[0].device)
+        if self._rows is None or self._rows.shape != lens.shape:
+            self._rows, self.lens, self.active = (torch.empty_like(lens) for _ in range(3))
+        self._rows.copy_(lens)
+        torch.add(lens, 1, out=self.lens)
+        self.active.fill_(1)
+        self.mode = "per_seq"
+
+    def reset(self):
+        """Start a new sequence in the same buffers (host mode, position 0)."""
+        self.pos, self.mode = 0, "host"
+
+    def snapshot(self):
+        """What a device-mode step changes, for ``restore`` (a warm-up or capture run of the step)."""
+        return (self.pos, self._rows.clone(), self.lens.clone()) if self.mode == "per_seq" else (self.pos,)
+
+    def restore(self, snap):
+        """Undo the steps since ``snapshot``: the position(s); the rows they wrote are not valid yet."""
+        self.pos = snap[0]
+        if self.mode == "per_seq":
+            self._rows.copy_(snap[1])
+            self.lens.copy_(snap[2])
+        else:
+            self._pos1.fill_(self.pos)
+            self.mask[..., self.pos:] = float("-inf")
+
+    def begin_step(self, T):
+        """Before ``T`` tokens are embedded and appended: device mode opens the mask at the write row,
+        the modes with a host position check the capacity."""
+        if self.mode == "device":
+            self.mask.index_fill_(2, self._pos1, 0.0)
+        elif self.mode == "per_seq" and T != 1:
+            raise ValueError("a cache in per-sequence mode takes one token per row and step")
+        elif self.pos + T > self.max_len:
+            raise ValueError(f"KV cache full: {self.pos} + {T} > {self.max_len}")
+
+    def end_step(self, T):
+        """After the LM head: advance the position(s), once per step (device mode: one token)."""
+        if self.mode == "device":
+            self._pos1.add_(1)
+            return
+        if self.mode == "per_seq":
+            self._rows.add_(self.active)
+            self.lens.add_(self.active)
+        self.pos += T
+
+    def embed(self, idx, wte, wpe):
+        """Token + position embedding of ``idx`` (B, T) at the cache position(s)."""
+        if self.mode == "host":
+            return ops.embedding(idx, wte, wpe[self.pos: self.pos + idx.shape[1]])
+        rows = wpe.index_select(0, self.pos_t)
+        if self.mode == "device":
+            return ops.embedding(idx, wte, rows)
+        # row b's position embedding is wpe[pos_t[b]]: the ids viewed as one sequence of B tokens
+        return ops.embedding(idx.view(1, -1), wte, rows).view(idx.shape[0], 1, -1)
+
+    def update(self, layer, kv):
+        """Append ``kv`` (B, T, 2, H, D) — the key / value slice of the packed QKV projection — at
+        the cache position; returns the (key, value) views the attention reads.  K and V share one
+        buffer per layer, so an append is ONE copy (slice copy_ / index_copy_ / scatter_ by mode)."""
+        buf = self.kv[layer]
+        if self.mode == "host":
+            B, T, _, H, D = kv.shape
+            if buf is None:
+                # zeroed, not empty: the device-mode step reads the WHOLE buffer under the key mask, and
+                # a masked row still enters P·V as 0 · v — a NaN bit pattern in an unwritten row would
+                # turn that into NaN
+                buf = self.kv[layer] = kv.new_zeros(B, self.max_len, 2, H, D)
+            buf[:, self.pos: self.pos + T].copy_(kv)
+            return buf[:, : self.pos + T, 0], buf[:, : self.pos + T, 1]
+        if self.mode == "device":
+            buf.index_copy_(1, self._pos1, kv)
+        else:  # each row at its own position
+            if kv.shape[1] != 1:
+                raise ValueError("KV cache in per-sequence mode appends one token per step")
+            buf.scatter_(1, self._rows.view(-1, 1, 1, 1, 1).expand_as(kv), kv)
+        return buf[:, :, 0], buf[:, :, 1]
+
+    def attend(self, q, k, v, causal):
+        """Attention of this step's queries (B, T, H, D) over the key / value views of the append."""
+        if self.mode == "per_seq":  # each row reads its own lens[b] keys
+            return ops.attention_decode(q, k, v, lens=self.lens)
+        if self.mode == "device":  # the key mask carries causality
+            return ops.attention_decode(q, k, v, self.mask) if q.shape[1] == 1 else ops.attention(q, k, v, bias=self.mask)
+        return ops.attention(q, k, v, causal=causal)
+
+
+def host_lens(name, lens, B, T):
+    """``lens`` (tensor or sequence) as B host integers in [1, T]."""
+    lens = [int(n) for n in (lens.tolist() if torch.is_tensor(lens) else lens)]
+    if len(lens) != B or min(lens) < 1 or max(lens) > T:
+        raise ValueError(f"{name} must hold {B} values in [1, {T}], got {lens}")
+    return lens
+
+
+def _sample(logits, temperature, top_k, generator, top_p=None):
+    """(B, V) fp32 logits → (B, 1) next-token ids: greedy (temperature 0), else sampling from the
+    temperature-scaled softmax restricted to the top-k logits and / or the smallest set of tokens
+    whose probability mass reaches top_p (nucleus)."""
+    if temperature == 0:
+        return logits.argmax(-1, keepdim=True)
+    logits = logits / temperature
+    if top_k is not None and top_k < logits.shape[-1]:
+        kth = torch.topk(logits, top_k, dim=-1).values[:, -1:]
+        logits = logits.masked_fill(logits < kth, float("-inf"))
+    if top_p is not None and top_p < 1.0:
+        srt, idx = torch.sort(logits, dim=-1, descending=True)
+        cum = torch.softmax(srt, -1).cumsum(-1)
+        drop = cum - torch.softmax(srt, -1) >= top_p  # mass BEFORE a token already reaches top_p
+        drop[..., 0] = False  # the most likely token always stays (top_p <= 0 would drop every token)
+        srt = srt.masked_fill(drop, float("-inf"))
+        logits = torch.full_like(logits, float("-inf")).scatter(-1, idx, srt)
+    probs = torch.softmax(logits, -1)
+    return torch.multinomial(probs, 1, generator=generator)
+
+
+# captured decode steps kept per model (least recently used evicted first): each holds a KV cache of
+# 2 · n_layer · B · length · n_embd elements (≈ 2.4 GB for GPT-2-small at B = 64, length 1024)
+DECODE_GRAPHS_MAX = int(os.environ.get("REPLICANN_DECODE_GRAPHS", "4"))
+DECODE_LEN_BUCKET = 64  # cache lengths are rounded up to this (capped at block_size): one graph per bucket
+DECODE_EOS_CHECK = 8  # ragged generate: "has every row finished?" is asked of the device every this many steps
+
+
+class _GraphRegistry(dict):
+    """One model's captured decode steps kept across ``generate`` calls, least recently used first:
+    (batch, cache length, dtype, device, parameter storage[, "ragged" for the per-sequence step]) →
+    (cache, graph, token buffer, logits), so a serving loop captures once per (batch, length bucket).
+    At most DECODE_GRAPHS_MAX (REPLICANN_DECODE_GRAPHS, default 4) are kept; each holds its KV cache."""
+
+    def lookup(self, model, B, L, ragged, use):
+        """(key, its stored entry — now the most recently used — or None).  The parameters' storage
+        is part of the key: a graph reads them by address, so entries captured before a parameter was
+        re-assigned (p.data = ...) are dropped here, whether or not this call will ``use`` a graph."""
+        sig = tuple(p.data_ptr() for p in model.parameters())
+        key = (B, L, model.wte.dtype, model.wte.device, sig) + (("ragged",) if ragged else ())
+        for k in [k for k in self if k[4] != sig]:
+            del self[k]
+        entry = self.pop(key, None) if use else None
+        if entry is not None:
+            self[key] = entry
+        return key, entry
+
+    def make_room(self):
+        while len(self) >= max(DECODE_GRAPHS_MAX, 1):
+            self.pop(next(iter(self)))
+
+
+# kept outside the module's attributes (weak-keyed), so copying / pickling a model never touches graph objects
+_REGISTRIES: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+
+
+def registry(model):
+    return _REGISTRIES.setdefault(model, _GraphRegistry())
+
+
+def capture_step(model, cache, B):
+    """Record the one-token decode step as a hipGraph (after one eager warm-up that tunes the
+    decode GEMM shapes); the caller writes the next token into ``tok`` and replays."""
+    dev = model.wte.device
+    tok = torch.zeros(B, 1, dtype=torch.long, device=dev)
+    if not cache.device_pos:  # uniform: the prefill ran in host mode (ragged: it left per-sequence mode)
+        cache.to_device_position()
+    snap = cache.snapshot()
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        model._device_position_step(tok, cache)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    cache.restore(snap)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = model._device_position_step(tok, cache)
+    cache.restore(snap)
+    return graph, tok, out
+
+
+class _StepDriver:
+    """One ``generate`` call's cache and one-token step.  With ``graph``, an earlier call's cache and
+    captured step of the same key are reused; failing that the first ``step`` captures (and stores) one."""
+
+    def __init__(self, model, B, length, ragged, graph):
+        c = model.config
+        if graph or ragged:  # one captured step (and cache) serves every length of a bucket
+            length = min(c.block_size, -(-length // DECODE_LEN_BUCKET) * DECODE_LEN_BUCKET)
+        self.model, self.B, self.graph, self.graphs = model, B, graph, registry(model)
+        self.key, self.entry = self.graphs.lookup(model, B, length, ragged, graph)
+        self.cache = KVCache(c.n_layer, length) if self.entry is None else self.entry[0]
+        self.cache.reset()
+
+    def step(self, tok):
+        """Logits (B, vocab) after appending ``tok`` (B, 1); a replay returns its static buffer."""
+        if not self.graph:
+            return self.model._device_position_step(tok, self.cache)
+        if self.entry is None:
+            self.graphs.make_room()  # before the capture allocates
+            self.entry = self.graphs[self.key] = (self.cache, *self.model._capture_decode(self.cache, self.B))
+        elif not self.cache.device_pos:  # a reused uniform cache: its prefill ran in host mode
+            self.cache.to_device_position()
+        _, graph, buf, out = self.entry
+        buf.copy_(tok)
+        graph.replay()
+        return out
+
+
+@torch.no_grad()
+def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=None, generator=None, graph=None,
+             prompt_lens=None, eos_token_id=None, pad_token_id=None):
+    """Autoregressive sampling with a KV cache: ``idx`` (B, T0) prompt → (B, T0 + max_new_tokens).
+    ``temperature`` 0 = greedy; ``top_k`` / ``top_p`` restrict sampling.  One prefill pass over the prompt, then one-token steps whose
+    attention reads the cached keys / values (no recomputation of the prefix).  ``graph``
+    (default: on for GPU models): the one-token step is captured once as a hipGraph and replayed
+    (per-step values live on the device), so a step costs its kernels, not ~130 host launches.
+
+    Ragged batches / stopping (either of ``prompt_lens``, ``eos_token_id`` given): ``idx`` is
+    right-padded, row b's prompt is ``idx[b, :prompt_lens[b]]`` (default: all of it) and whatever the
+    padding holds is ignored.  A row is finished once it has emitted ``eos_token_id`` (kept in the
+    output); from then on it emits ``pad_token_id`` (default: the EOS id, else 0) and its position
+    stops.  Generation ends early once every row is finished (asked of the device every
+    DECODE_EOS_CHECK steps).  Returns ``(tokens, lens)``: tokens (B, max(lens)), rows
+    ``prompt_b ‖ generated_b`` right-padded with the pad id, and lens (B,) each row's total length."""
+    B, T0 = idx.shape
+    ragged = prompt_lens is not None or eos_token_id is not None
+    if top_p is not None and not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    plens = [T0] * B if prompt_lens is None else host_lens("prompt_lens", prompt_lens, B, T0)
+    Tm = max(plens)
+    if ragged and max_new_tokens < 1:
+        raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
+    if Tm + max_new_tokens > model.config.block_size:
+        raise ValueError(f"prompt {Tm} + {max_new_tokens} new tokens exceeds block_size {model.config.block_size}")
+    use_graph = (model.wte.is_cuda if graph is None else graph) and max_new_tokens > 2
+    was_training = model.training
+    model.eval()
+    try:
+        driver = _StepDriver(model, B, Tm + max_new_tokens, ragged, use_graph)
+        sampling = (temperature, top_k, generator, top_p)
+        if ragged:
+            return _ragged_loop(driver, idx[:, :Tm], plens, max_new_tokens, eos_token_id, pad_token_id, sampling)
+        logits = model.decode_step(idx, driver.cache)
+        out = [idx]
+        for i in range(max_new_tokens):
+            out.append(_sample(logits.float(), *sampling))
+            if i + 1 < max_new_tokens:
+                logits = driver.step(out[-1])
+        return torch.cat(out, 1)
+    finally:
+        model.train(was_training)
+
+
+def _ragged_loop(driver, idx, plens, max_new_tokens, eos, pad, sampling):
+    (B, Tm), dev = idx.shape, idx.device  # idx: the prompts cut to the longest one
+    if pad is None:
+        pad = eos if eos is not None else 0
+    lens = torch.tensor(plens, dtype=torch.long, device=dev)  # each row's length so far
+    # rows prompt ‖ generated, pad elsewhere (one spare column: a finished row's write lands in range)
+    tokens = torch.full((B, Tm + max_new_tokens + 1), pad, dtype=torch.long, device=dev)
+    keep = torch.arange(Tm, device=dev).unsqueeze(0) < lens.unsqueeze(1)
+    tokens[:, :Tm] = torch.where(keep, idx, tokens[:, :Tm])
+    finished = torch.zeros(B, dtype=torch.bool, device=dev)
+    logits = driver.model.decode_step(idx, driver.cache, lens=plens)
+    for i in range(max_new_tokens):
+        nxt = _sample(logits.float(), *sampling)
+        nxt = torch.where(finished.unsqueeze(1), torch.full_like(nxt, pad), nxt)  # finished rows emit pad
+        tokens.scatter_(1, lens.unsqueeze(1), nxt)
+        lens += ~finished
+        if eos is not None:
+            finished |= nxt.squeeze(1) == eos
+        if i + 1 == max_new_tokens:
+            break
+        if eos is not None and (i + 1) % DECODE_EOS_CHECK == 0 and bool(finished.all()):
+            break  # the one host sync of the stop logic
+        driver.cache.active.copy_(~finished)  # finished rows stay where they are
+        logits = driver.step(nxt)
+    return tokens[:, : int(lens.max())], lens
+
+
+def generate_batch(model, prompts, max_new_tokens, **kw):
+    """``generate`` for a list of 1-D token tensors of any lengths: pads them, runs the ragged
+    path and returns a list of 1-D tensors ``prompt_b ‖ generated_b``, each trimmed to its length."""
+    plens = [int(p.numel()) for p in prompts]
+    if not plens or min(plens) < 1:
+        raise ValueError("generate_batch needs at least one prompt, each of at least one token")
+    idx = torch.zeros(len(prompts), max(plens), dtype=torch.long, device=model.wte.device)
+    for b, p in enumerate(prompts):
+        idx[b, : plens[b]] = p.to(idx.device)
+    tokens, lens = model.generate(idx, max_new_tokens, prompt_lens=plens, **kw)
+    return [tokens[b, :n] for b, n in enumerate(lens.tolist())]

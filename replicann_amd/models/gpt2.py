@@ -17,14 +17,15 @@ MI355X-specific choices:
 from __future__ import annotations
 
 import os
-import weakref
 from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
 
 from .. import ops
-from .blocks import Fp8Slots, KVCache, LayerNorm, PreLNBlock
+from . import decoding
+from .blocks import Fp8Slots, LayerNorm, PreLNBlock
+from .decoding import DECODE_EOS_CHECK, DECODE_GRAPHS_MAX, DECODE_LEN_BUCKET, _sample  # noqa: F401  (re-exported)
 
 
 @dataclass(frozen=True)
@@ -76,14 +77,6 @@ class GPT2Config:
         d = dict(n_layer=2, n_head=4, n_embd=128, block_size=128, vocab_size=1000, vocab_pad=1024)
         d.update(kw)
         return GPT2Config(**d)
-
-
-_DECODE_GRAPHS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-# captured decode steps kept per model (least recently used evicted first): each holds a KV cache of
-# 2 · n_layer · B · length · n_embd elements (≈ 2.4 GB for GPT-2-small at B = 64, length 1024)
-DECODE_GRAPHS_MAX = int(os.environ.get("REPLICANN_DECODE_GRAPHS", "4"))
-DECODE_LEN_BUCKET = 64  # cache lengths are rounded up to this (capped at block_size): one graph per bucket
-DECODE_EOS_CHECK = 8  # ragged generate: "has every row finished?" is asked of the device every this many steps
 
 
 class GPT2(nn.Module):
@@ -159,10 +152,22 @@ class GPT2(nn.Module):
                                         chunk_rows=self.config.ce_chunk, fp8=fp8h,
                                         fp8_logits=self.config.fp8_head != 2)
 
+    def _hidden_cached(self, idx, cache):
+        """Final-LayerNorm output (B, T, n_embd) of ``idx`` (B, T) appended to ``cache``: the one
+        cached pass, in whichever mode the cache is (prefill and every form of the one-token step)."""
+        cache.begin_step(idx.shape[1])
+        x = cache.embed(idx, self.wte, self.wpe)
+        prev = None
+        for i, blk in enumerate(self.h):
+            x = blk(x, prev, cache=cache, layer=i)
+            prev = blk.out_bias()
+        return self.ln_f(x, producer_bias=prev)
+
     @torch.no_grad()
     def decode_step(self, idx, cache, lens=None):
         """Logits (B, vocab) of the LAST position of ``idx`` (B, T) appended at ``cache.pos``:
-        prefill (T = prompt length) and one-token decode steps share this path.
+        prefill (T = prompt length) and one-token decode steps share this path.  In the cache's device
+        modes (``decoding.KVCache``) a one-token step uses no host value: capturable as a hipGraph.
 
         ``lens`` (B host integers, 1 <= lens[b] <= T): ``idx`` is a right-padded batch of prompts of
         these lengths, prefilled into an empty cache.  The pass is the same causal one — causality
@@ -171,271 +176,38 @@ class GPT2(nn.Module):
         The logits are those of each row's own last valid position, and the cache is left in
         per-sequence mode at position lens[b]: later ``decode_step(tok (B, 1), cache)`` calls advance
         every active row at its own position."""
-        c = self.config
-        T = idx.shape[1]
-        if lens is not None:
-            return self._ragged_prefill(idx, cache, lens)
-        if cache.per_seq:
-            if T != 1:
-                raise ValueError("a cache in per-sequence mode takes one token per row and step")
-            if cache.pos + 1 > cache.max_len:
-                raise ValueError(f"KV cache full: {cache.pos} + 1 > {cache.max_len}")
-            return self._device_position_step(idx, cache)
-        x = ops.embedding(idx, self.wte, self.wpe[cache.pos: cache.pos + T])
-        prev = None
-        for i, blk in enumerate(self.h):
-            x = blk(x, prev, cache=cache, layer=i)
-            prev = blk.out_bias()
-        h = self.ln_f(x, producer_bias=prev)
-        cache.advance(T)
-        return ops.linear(h[:, -1:].contiguous(), self.wte)[:, 0, : c.vocab_size]
-
-    @torch.no_grad()
-    def _ragged_prefill(self, idx, cache, lens):
-        c = self.config
         B, T = idx.shape
-        lens = [int(n) for n in (lens.tolist() if torch.is_tensor(lens) else lens)]
-        if len(lens) != B or min(lens) < 1 or max(lens) > T:
-            raise ValueError(f"lens must hold {B} values in [1, {T}], got {lens}")
-        if cache.pos != 0 or cache.device_pos:
-            raise ValueError("a ragged prefill needs an empty cache (KVCache.reset())")
-        x = ops.embedding(idx, self.wte, self.wpe[:T])
-        prev = None
-        for i, blk in enumerate(self.h):
-            x = blk(x, prev, cache=cache, layer=i)
-            prev = blk.out_bias()
-        h = self.ln_f(x, producer_bias=prev)
-        cache.to_per_sequence(lens)
-        # each row's own last valid position, gathered BEFORE the LM head: the head runs on B rows
-        last = h[torch.arange(B, device=h.device), cache.pos_t - 1].unsqueeze(1).contiguous()
-        return ops.linear(last, self.wte)[:, 0, : c.vocab_size]
-
-    @torch.no_grad()
-    def _device_position_step(self, tok, cache):
-        """One-token decode step with every per-step value on the device (``KVCache`` device-position
-        mode): capturable as a hipGraph.  Reads ``tok`` (B, 1), returns (B, vocab) logits, advances
-        ``cache.pos_t``.  In per-sequence mode every row is appended, embedded and attended at its own
-        position, and only the rows of ``cache.active`` advance."""
-        c = self.config
-        if cache.per_seq:
-            # row b's position embedding is wpe[pos_t[b]]: the ids viewed as one sequence of B tokens
-            x = ops.embedding(tok.view(1, -1), self.wte, self.wpe.index_select(0, cache.pos_t)).view(tok.shape[0], 1, -1)
-        else:
-            cache.mask.index_fill_(2, cache.pos_t, 0.0)
-            x = ops.embedding(tok, self.wte, self.wpe.index_select(0, cache.pos_t))
-        prev = None
-        for i, blk in enumerate(self.h):
-            x = blk(x, prev, cache=cache, layer=i)
-            prev = blk.out_bias()
-        h = self.ln_f(x, producer_bias=prev)
-        logits = ops.linear(h, self.wte)[:, 0, : c.vocab_size]
-        cache.step()
+        if lens is not None:
+            lens = decoding.host_lens("lens", lens, B, T)
+            if cache.pos != 0 or cache.mode != "host":
+                raise ValueError("a ragged prefill needs an empty cache (KVCache.reset())")
+        h = self._hidden_cached(idx, cache)
+        if lens is not None:
+            cache.to_per_sequence(lens)
+            # each row's own last valid position, gathered BEFORE the LM head: the head runs on B rows
+            last = h[torch.arange(B, device=h.device), cache.pos_t - 1].unsqueeze(1).contiguous()
+            return ops.linear(last, self.wte)[:, 0, : self.config.vocab_size]
+        logits = ops.linear(h[:, -1:].contiguous(), self.wte)[:, 0, : self.config.vocab_size]
+        cache.end_step(T)
         return logits
 
+    def _device_position_step(self, tok, cache):
+        """The one-token step ``tok`` (B, 1) → (B, vocab) logits that ``generate`` runs or captures."""
+        return self.decode_step(tok, cache)
+
     def _capture_decode(self, cache, B):
-        """Record the one-token decode step as a hipGraph (after one eager warm-up that tunes the
-        decode GEMM shapes); the caller writes the next token into ``tok`` and replays."""
-        dev = self.wte.device
-        tok = torch.zeros(B, 1, dtype=torch.long, device=dev)
-        pos0 = cache.pos
-        if cache.per_seq:  # ragged: the cache left its prefill in per-sequence mode
-            pos_t0, lens0 = cache.pos_t.clone(), cache.lens.clone()
+        return decoding.capture_step(self, cache, B)
 
-            def reset():  # the warm-up wrote each row's next (not yet valid) cache row and advanced: undo
-                cache.pos_t.copy_(pos_t0)
-                cache.lens.copy_(lens0)
-                cache.pos = pos0
-        else:
-            cache.to_device_position()
-
-            def reset():  # the warm-up wrote row pos0 and advanced the position: undo
-                cache.pos_t.fill_(pos0)
-                cache.mask[..., pos0:] = float("-inf")
-
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._device_position_step(tok, cache)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        reset()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self._device_position_step(tok, cache)
-        reset()
-        return graph, tok, out
-
-    @torch.no_grad()
-    def generate(self, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=None, generator=None, graph=None,
-                 prompt_lens=None, eos_token_id=None, pad_token_id=None):
-        """Autoregressive sampling with a KV cache: ``idx`` (B, T0) prompt → (B, T0 + max_new_tokens).
-        ``temperature`` 0 = greedy; ``top_k`` / ``top_p`` restrict sampling.  One prefill pass over the prompt, then one-token steps whose
-        attention reads the cached keys / values (no recomputation of the prefix).  ``graph``
-        (default: on for GPU models): the one-token step is captured once as a hipGraph and replayed
-        (per-step values live on the device), so a step costs its kernels, not ~130 host launches.
-
-        Ragged batches / stopping (either of ``prompt_lens``, ``eos_token_id`` given): ``idx`` is
-        right-padded, row b's prompt is ``idx[b, :prompt_lens[b]]`` (default: all of it) and whatever the
-        padding holds is ignored.  A row is finished once it has emitted ``eos_token_id`` (kept in the
-        output); from then on it emits ``pad_token_id`` (default: the EOS id, else 0) and its position
-        stops.  Generation ends early once every row is finished (asked of the device every
-        DECODE_EOS_CHECK steps).  Returns ``(tokens, lens)``: tokens (B, max(lens)), rows
-        ``prompt_b ‖ generated_b`` right-padded with the pad id, and lens (B,) each row's total length."""
-        c = self.config
-        B, T0 = idx.shape
-        if prompt_lens is not None or eos_token_id is not None:
-            if top_p is not None and not 0.0 < top_p <= 1.0:
-                raise ValueError(f"top_p must be in (0, 1], got {top_p}")
-            return self._generate_ragged(idx, max_new_tokens, prompt_lens, eos_token_id, pad_token_id,
-                                         dict(temperature=temperature, top_k=top_k, generator=generator, top_p=top_p),
-                                         graph)
-        if T0 + max_new_tokens > c.block_size:
-            raise ValueError(f"prompt {T0} + {max_new_tokens} new tokens exceeds block_size {c.block_size}")
-        if top_p is not None and not 0.0 < top_p <= 1.0:
-            raise ValueError(f"top_p must be in (0, 1], got {top_p}")
-        use_graph = (self.wte.is_cuda if graph is None else graph) and max_new_tokens > 2
-        was_training = self.training
-        self.eval()
-        try:
-            L = T0 + max_new_tokens
-            if use_graph:  # one captured step (and cache) serves every length of a bucket
-                L = min(c.block_size, -(-L // DECODE_LEN_BUCKET) * DECODE_LEN_BUCKET)
-            # the parameters' storage is part of the key: a graph reads them by address, so one captured
-            # before a parameter was re-assigned (p.data = ...) must never be replayed
-            sig = tuple(p.data_ptr() for p in self.parameters())
-            key = (B, L, self.wte.dtype, self.wte.device, sig)
-            graphs, entry = self._graph_entry(key, use_graph)
-            if entry is not None:  # same batch / length as an earlier call: reuse its cache and graph
-                cache = entry[0]
-                cache.reset()
-            else:
-                cache = KVCache(c.n_layer, L)
-            logits = self.decode_step(idx, cache)
-            out = [idx]
-            for i in range(max_new_tokens):
-                nxt = _sample(logits.float(), temperature, top_k, generator, top_p)
-                out.append(nxt)
-                if i + 1 == max_new_tokens:
-                    break
-                if use_graph:
-                    if entry is None:
-                        while len(graphs) >= max(DECODE_GRAPHS_MAX, 1):  # bounded: evict the least recently used
-                            graphs.pop(next(iter(graphs)))
-                        entry = (cache, *self._capture_decode(cache, B))
-                        graphs[key] = entry
-                    elif not cache.device_pos:
-                        cache.to_device_position()
-                    _, g, tok, g_out = entry
-                    tok.copy_(nxt)
-                    g.replay()
-                    logits = g_out
-                else:
-                    logits = self.decode_step(nxt, cache)
-            return torch.cat(out, 1)
-        finally:
-            self.train(was_training)
-
-    def _graph_entry(self, key, use_graph):
-        """(registry, stored entry or None) for ``key``; entries captured on re-assigned parameters
-        (key[4], the storage signature) are dropped, a hit becomes the most recently used."""
-        graphs = self._decode_graphs()
-        for k in [k for k in graphs if k[4] != key[4]]:
-            del graphs[k]
-        entry = graphs.pop(key, None) if use_graph else None
-        if entry is not None:
-            graphs[key] = entry
-        return graphs, entry
-
-    @torch.no_grad()
-    def _generate_ragged(self, idx, max_new_tokens, prompt_lens, eos, pad, sample_kw, graph):
-        c = self.config
-        B, T0 = idx.shape
-        dev = idx.device
-        if prompt_lens is None:
-            plens = [T0] * B
-        else:
-            plens = [int(n) for n in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
-        if len(plens) != B or min(plens) < 1 or max(plens) > T0:
-            raise ValueError(f"prompt_lens must hold {B} values in [1, {T0}], got {plens}")
-        Tm = max(plens)
-        if max_new_tokens < 1:
-            raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
-        if Tm + max_new_tokens > c.block_size:
-            raise ValueError(f"prompt {Tm} + {max_new_tokens} new tokens exceeds block_size {c.block_size}")
-        if pad is None:
-            pad = eos if eos is not None else 0
-        use_graph = (self.wte.is_cuda if graph is None else graph) and max_new_tokens > 2
-        was_training = self.training
-        self.eval()
-        try:
-            L = min(c.block_size, -(-(Tm + max_new_tokens) // DECODE_LEN_BUCKET) * DECODE_LEN_BUCKET)
-            sig = tuple(p.data_ptr() for p in self.parameters())
-            key = (B, L, self.wte.dtype, self.wte.device, sig, "ragged")  # the mode last: k[4] stays the storage
-            graphs, entry = self._graph_entry(key, use_graph)
-            if entry is not None:
-                cache = entry[0]
-                cache.reset()
-            else:
-                cache = KVCache(c.n_layer, L)
-            lens = torch.tensor(plens, dtype=torch.long, device=dev)  # each row's length so far
-            # rows prompt ‖ generated, pad elsewhere (one spare column: a finished row's write lands in range)
-            tokens = torch.full((B, Tm + max_new_tokens + 1), pad, dtype=torch.long, device=dev)
-            keep = torch.arange(Tm, device=dev).unsqueeze(0) < lens.unsqueeze(1)
-            tokens[:, :Tm] = torch.where(keep, idx[:, :Tm], tokens[:, :Tm])
-            finished = torch.zeros(B, dtype=torch.bool, device=dev)
-            logits = self.decode_step(idx[:, :Tm], cache, lens=plens)
-            for i in range(max_new_tokens):
-                nxt = _sample(logits.float(), **sample_kw)
-                nxt = torch.where(finished.unsqueeze(1), torch.full_like(nxt, pad), nxt)  # finished rows emit pad
-                tokens.scatter_(1, lens.unsqueeze(1), nxt)
-                lens += ~finished
-                if eos is not None:
-                    finished |= nxt.squeeze(1) == eos
-                if i + 1 == max_new_tokens:
-                    break
-                if eos is not None and (i + 1) % DECODE_EOS_CHECK == 0 and bool(finished.all()):
-                    break  # the one host sync of the stop logic
-                cache.active.copy_(~finished)  # finished rows stay where they are
-                if use_graph:
-                    if entry is None:
-                        while len(graphs) >= max(DECODE_GRAPHS_MAX, 1):  # bounded: evict the least recently used
-                            graphs.pop(next(iter(graphs)))
-                        entry = (cache, *self._capture_decode(cache, B))
-                        graphs[key] = entry
-                    _, g, tok, g_out = entry
-                    tok.copy_(nxt)
-                    g.replay()
-                    logits = g_out
-                else:
-                    logits = self._device_position_step(nxt, cache)
-            return tokens[:, : int(lens.max())], lens
-        finally:
-            self.train(was_training)
-
-    def generate_batch(self, prompts, max_new_tokens, **kw):
-        """``generate`` for a list of 1-D token tensors of any lengths: pads them, runs the ragged
-        path and returns a list of 1-D tensors ``prompt_b ‖ generated_b``, each trimmed to its length."""
-        plens = [int(p.numel()) for p in prompts]
-        if not plens or min(plens) < 1:
-            raise ValueError("generate_batch needs at least one prompt, each of at least one token")
-        idx = torch.zeros(len(prompts), max(plens), dtype=torch.long, device=self.wte.device)
-        for b, p in enumerate(prompts):
-            idx[b, : plens[b]] = p.to(idx.device)
-        tokens, lens = self.generate(idx, max_new_tokens, prompt_lens=plens, **kw)
-        return [tokens[b, :n] for b, n in enumerate(lens.tolist())]
+    # generation itself (the cache, the sampling loops, the captured-step registry): models/decoding.py
+    generate = decoding.generate
+    generate_batch = decoding.generate_batch
 
     def _decode_graphs(self):
-        """Captured decode steps kept across ``generate`` calls, keyed by (batch, cache length rounded
-        up to DECODE_LEN_BUCKET, dtype, device, parameter storage[, "ragged" for the per-sequence step]):
-        a serving loop captures once per
-        (batch, length bucket).  At most DECODE_GRAPHS_MAX (REPLICANN_DECODE_GRAPHS, default 4) are
-        kept, least recently used evicted first.  Each holds its KV cache (2 · n_layer · B · length ·
-        n_embd elements); ``clear_decode_graphs`` frees them.  Kept
-        outside the module's attributes (a weak-keyed registry), so copying / pickling the model
-        never touches graph objects."""
-        return _DECODE_GRAPHS.setdefault(self, {})
+        """The captured decode steps kept across ``generate`` calls (``decoding._GraphRegistry``)."""
+        return decoding.registry(self)
 
     def clear_decode_graphs(self):
-        _DECODE_GRAPHS.pop(self, None)
+        decoding.registry(self).clear()
 
     def flops_per_token(self, T=None):
         """Training FLOPs per token (fwd+bwd): 6·N_matmul + attention (causal)."""
@@ -445,23 +217,3 @@ class GPT2(nn.Module):
         attn = c.n_layer * 2 * 2 * T * c.n_embd * 0.5  # fwd, causal ≈ half
         return 6 * n_mm + 3 * attn
 
-
-def _sample(logits, temperature, top_k, generator, top_p=None):
-    """(B, V) fp32 logits → (B, 1) next-token ids: greedy (temperature 0), else sampling from the
-    temperature-scaled softmax restricted to the top-k logits and / or the smallest set of tokens
-    whose probability mass reaches top_p (nucleus)."""
-    if temperature == 0:
-        return logits.argmax(-1, keepdim=True)
-    logits = logits / temperature
-    if top_k is not None and top_k < logits.shape[-1]:
-        kth = torch.topk(logits, top_k, dim=-1).values[:, -1:]
-        logits = logits.masked_fill(logits < kth, float("-inf"))
-    if top_p is not None and top_p < 1.0:
-        srt, idx = torch.sort(logits, dim=-1, descending=True)
-        cum = torch.softmax(srt, -1).cumsum(-1)
-        drop = cum - torch.softmax(srt, -1) >= top_p  # mass BEFORE a token already reaches top_p
-        drop[..., 0] = False  # the most likely token always stays (top_p <= 0 would drop every token)
-        srt = srt.masked_fill(drop, float("-inf"))
-        logits = torch.full_like(logits, float("-inf")).scatter(-1, idx, srt)
-    probs = torch.softmax(logits, -1)
-    return torch.multinomial(probs, 1, generator=generator)

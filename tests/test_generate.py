@@ -81,6 +81,97 @@ def test_device_position_steps_match_host_position():
     assert int(dev.pos_t) == 20 and bool((dev.mask == 0).all())
 
 
+RAGGED = [5, 20, 13]
+
+
+def _model2():
+    torch.manual_seed(0)
+    return GPT2(GPT2Config.tiny(n_head=2)).eval()
+
+
+def _device_run(m, seq, cache):
+    """Uniform prefill of 12 tokens, device mode, two steps: (pos_t / mask addresses, the steps' logits)."""
+    m.decode_step(seq[:, :12], cache)
+    cache.to_device_position()
+    ptrs = (cache.pos_t.data_ptr(), cache.mask.data_ptr())
+    return ptrs, [m.decode_step(seq[:, t:t + 1], cache).clone() for t in (12, 13)]
+
+
+def _ragged_run(m, seq, cache):
+    """Ragged prefill at RAGGED, two steps: the per-sequence tensors' addresses."""
+    m.decode_step(seq[:, :20], cache, lens=RAGGED)
+    ptrs = tuple(t.data_ptr() for t in (cache.pos_t, cache.lens, cache.active))
+    for t in (20, 20):
+        m.decode_step(seq[:, t:t + 1], cache)
+    return ptrs
+
+
+def test_cache_tensors_survive_mode_changes():
+    """The tensors a captured step reads by address are allocated once per cache: the same storage at
+    every entry into a mode, whatever modes came between; and nothing of those modes leaks into the
+    results."""
+    m = _model2()
+    seq = torch.randint(0, 1000, (3, 21))
+    cache = KVCache(m.config.n_layer, 32)
+    dev1, _ = _device_run(m, seq, cache)
+    assert int(cache.pos_t) == 14
+    cache.reset()
+    seq1 = _ragged_run(m, seq, cache)
+    assert cache.pos_t.tolist() == [n + 2 for n in RAGGED] and cache.pos == max(RAGGED) + 2
+    cache.reset()
+    dev2, logits = _device_run(m, seq, cache)
+    assert dev2 == dev1
+    _, fresh = _device_run(m, seq, KVCache(m.config.n_layer, 32))
+    assert all(torch.equal(a, b) for a, b in zip(logits, fresh))
+    cache.reset()
+    assert _ragged_run(m, seq, cache) == seq1
+
+
+def test_cache_mode_is_single_valued():
+    m = _model2()
+    seq = torch.randint(0, 1000, (3, 21))
+    cache = KVCache(m.config.n_layer, 32)
+    legal = {("host", False, False), ("device", True, False), ("per_seq", True, True)}
+
+    def state():
+        assert (cache.mode, cache.device_pos, cache.per_seq) in legal
+        return cache.mode
+
+    assert state() == "host" and cache.pos_t is None
+    m.decode_step(seq[:, :12], cache)
+    assert state() == "host"
+    cache.to_device_position()
+    assert state() == "device" and cache.pos_t.shape == (1,)
+    m.decode_step(seq[:, 12:13], cache)
+    assert state() == "device"
+    cache.reset()
+    assert state() == "host"
+    m.decode_step(seq[:, :20], cache, lens=RAGGED)
+    assert state() == "per_seq" and cache.pos_t.shape == (3,)
+    m.decode_step(seq[:, 20:21], cache)
+    assert state() == "per_seq"
+    with pytest.raises(ValueError):  # one token per row and step: the append itself and the step
+        cache.update(0, cache.kv[0][:, :2].clone())
+    with pytest.raises(ValueError):
+        m.decode_step(seq[:, :2], cache)
+    cache.reset()
+    assert state() == "host"
+
+
+def test_generate_uniform_ragged_uniform_on_one_model():
+    """Both generation loops run over one step driver: alternating them on one model (same batch,
+    same length bucket) gives what each call gives on a fresh copy of the model."""
+    import copy
+    m = _model2()
+    idx = torch.randint(0, 1000, (3, 15))
+    calls = [dict(), dict(prompt_lens=[5, 15, 13]), dict()]
+    got = [m.generate(idx, 6, temperature=0, graph=False, **kw) for kw in calls]
+    want = [copy.deepcopy(m).generate(idx, 6, temperature=0, graph=False, **kw) for kw in calls]
+    assert torch.equal(got[0], want[0]) and torch.equal(got[2], want[2]) and torch.equal(got[0], got[2])
+    assert torch.equal(got[1][0], want[1][0]) and torch.equal(got[1][1], want[1][1])
+    assert got[1][1].tolist() == [11, 21, 19]
+
+
 def test_generate_cli_from_checkpoint(tmp_path, capsys):
     """``python -m replicann generate`` loads a training checkpoint (weights_only) and reproduces the
     model's own greedy continuation."""
