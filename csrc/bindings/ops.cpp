@@ -70,6 +70,8 @@ int rn_gemm_cfg_bm(int);
 long rn_gemm_colpart_rows(int, int);
 int rn_attn_decode(const void*, const void*, const void*, const float*, const void*, int, void*, int, int, int, int,
                    const long*, float, hipStream_t);
+int rn_sample_logits(const void*, int, long, int, int, float, int, float, const float*, const float*, const uint64_t*,
+                     int64_t*, int*, hipStream_t);
 int rn_gemm_skinny_kv(const void*, const void*, const void*, void*, int, int, int, long, long, long, void*,
                       const int64_t*, int, int, long, long, int, hipStream_t);
 int rn_attn_fwd(const void*, const void*, const void*, void*, float*, const float*, int, const long*, int, int, int,
@@ -799,6 +801,54 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const opti
     return o;
 }
 
+// fused token sampler (sampling.hip): logits (B, V) bf16 / fp32 with a unit column stride and a row
+// stride >= V (a column slice of a wider buffer is fine) -> (tokens (B, 1) int64, kept (B,) int32).
+// Exactly one of u ((B,) fp32 uniforms) and seed_buf (row b draws hash_uniform(seed, b)); params: 3
+// fp32 on the device (temperature, top_k, top_p) that override the host values, so that one captured
+// graph serves every setting.
+std::tuple<Tensor, Tensor> sample_logits(const Tensor& logits, double temperature, int64_t top_k, double top_p,
+                                         const optional<Tensor>& u, const optional<Tensor>& seed_buf,
+                                         const optional<Tensor>& params) {
+    CHECK_CUDA(logits); GUARD(logits);
+    TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat,
+                "sample_logits: logits must be bfloat16 or float32, got ", logits.scalar_type());
+    TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1, "sample_logits: logits must be (B, V >= 1), got ",
+                logits.sizes());
+    const int64_t B = logits.size(0), V = logits.size(1);
+    TORCH_CHECK(V <= (1 << 30), "sample_logits: V = ", V, " exceeds 2^30");
+    TORCH_CHECK(logits.stride(1) == 1 && (B == 1 || logits.stride(0) >= V),
+                "sample_logits: logits need a unit column stride and a row stride >= V, got strides ",
+                logits.strides());
+    TORCH_CHECK(temperature >= 0.0 && temperature < INFINITY, "sample_logits: temperature must be finite and >= 0, got ",
+                temperature);
+    TORCH_CHECK(top_k >= 0, "sample_logits: top_k must be >= 0 (0 = off), got ", top_k);
+    TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "sample_logits: top_p must be in (0, 1], got ", top_p);
+    const bool has_u = u && u->defined(), has_seed = seed_buf && seed_buf->defined();
+    TORCH_CHECK(has_u != has_seed, "sample_logits: exactly one of u and seed_buf must be given");
+    if (has_u)
+        TORCH_CHECK(u->scalar_type() == at::kFloat && u->dim() == 1 && u->size(0) == B && u->is_contiguous() &&
+                        u->device() == logits.device(),
+                    "sample_logits: u must be a contiguous (B,) float32 tensor on the logits' device");
+    const uint64_t* seed = seed_ptr(seed_buf);
+    if (has_seed) TORCH_CHECK(seed_buf->device() == logits.device(), "sample_logits: seed_buf must be on the logits' device");
+    const bool has_params = params && params->defined();
+    if (has_params)
+        TORCH_CHECK(params->scalar_type() == at::kFloat && params->numel() == 3 && params->is_contiguous() &&
+                        params->device() == logits.device(),
+                    "sample_logits: params must be 3 contiguous float32 values (temperature, top_k, top_p) on the "
+                    "logits' device");
+    Tensor tokens = at::empty({B, 1}, logits.options().dtype(at::kLong));
+    Tensor kept = at::empty({B}, logits.options().dtype(at::kInt));
+    if (B == 0) return {tokens, kept};
+    const int rc = rn_sample_logits(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, B == 1 ? V : logits.stride(0),
+                                    (int)B, (int)V, (float)temperature, (int)std::min<int64_t>(top_k, 1 << 30),
+                                    (float)top_p, has_params ? params->data_ptr<float>() : nullptr,
+                                    has_u ? u->data_ptr<float>() : nullptr, seed, tokens.data_ptr<int64_t>(),
+                                    kept.data_ptr<int>(), cur_stream());
+    TORCH_CHECK(rc == 0, "sample_logits: unsupported arguments (B=", B, ", V=", V, ")");
+    return {tokens, kept};
+}
+
 std::tuple<Tensor, Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& bias,
                                     double scale, bool causal, double p, int64_t seed,
                                     const optional<Tensor>& seed_buf) {
@@ -1296,6 +1346,8 @@ TORCH_LIBRARY(replicann, m) {
     m.def("act_bwd(Tensor dy, Tensor x, int kind) -> Tensor");
     m.def("dropout_fwd(Tensor x, float p, int seed, Tensor? seed_buf=None) -> Tensor");
     m.def("rng_next(Tensor(a!) state, Tensor(b!) out) -> ()");
+    m.def("sample_logits(Tensor logits, float temperature, int top_k, float top_p, Tensor? u, Tensor? seed_buf, "
+          "Tensor? params) -> (Tensor, Tensor)");
     m.def("add_act(Tensor a, Tensor b, bool relu) -> Tensor");
     m.def("softmax_fwd(Tensor x, float scale) -> Tensor");
     m.def("softmax_bwd(Tensor dy, Tensor y, float scale) -> Tensor");
@@ -1379,6 +1431,7 @@ TORCH_LIBRARY_IMPL(replicann, CUDA, m) {
     m.impl("act_bwd", &act_bwd);
     m.impl("dropout_fwd", &dropout_fwd);
     m.impl("rng_next", &rng_next);
+    m.impl("sample_logits", &sample_logits);
     m.impl("add_act", &add_act);
     m.impl("softmax_fwd", &softmax_fwd);
     m.impl("softmax_bwd", &softmax_bwd);

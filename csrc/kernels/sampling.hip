@@ -1,0 +1,383 @@
+// Fused token sampler: temperature, top-k, top-p (nucleus) and the draw, one launch per decode step.
+//
+// One workgroup of 1024 threads per row of logits (B, V).  Each thread reads its share of the row
+// ONCE, as 16-byte vectors, into registers (R rounds of one vector: 56 values per thread at
+// V = 50257) as order-preserving integer keys, and everything below runs from those registers:
+//
+//   max / argmax   one block reduce of (key, ~index): the largest key, lowest index on ties
+//   top-k          the k-th largest key by radix select with ONE-BIT digits: for every key bit from
+//                  the top, count the keys >= prefix | bit (block reduce of integers) and keep the
+//                  bit when at least k are.  At most 16 counts for bf16, 32 for fp32, and a pass
+//                  over the row only for the bits on which the maximum and a lower bound (the
+//                  k-th largest of the 1024 thread maxima, found the same way from one key per
+//                  thread) differ.  No LDS histogram: bf16 logits cluster in a handful of 8-bit
+//                  digits, where LDS atomics serialise.
+//   top-p          the same select weighted by e = exp((x - max) / T): the largest threshold t whose
+//                  mass of keys >= t still reaches top_p · Z (passes only between the top-k
+//                  threshold and the maximum).  Exactly "keep a token iff the mass of
+//                  the strictly greater logits is < top_p": whole tie groups stay or go.
+//   draw           inverse CDF in vocabulary index order, three levels: round totals -> one block
+//                  scan inside the hit round -> the owning thread's vector.
+//
+// Determinism: counts are integers, every float sum is a fixed tree (thread order, xor butterfly,
+// 16 wave partials in order) — no atomics at all, so equal inputs give equal outputs bitwise.
+// The draw is robust to the different association of its levels: a level picks the first unit with
+// cumulative mass > u·Z AND mass > 0, else its last unit with mass > 0, so the token returned is
+// always a kept one of non-zero probability (never a -inf logit), at most a rounding away from the
+// exact inverse CDF.
+//
+// Rows longer than the register budget (V + 7 > 57344) re-read the row from global memory in every
+// pass (R = 0): that path only has to be correct.
+#include "common.h"
+
+namespace {
+
+constexpr int SMP_T = 1024, SMP_W = SMP_T / RN_WAVE;
+
+// order-preserving image of a float: a > b  <=>  key(a) > key(b); NaN counts as -inf, -0 as +0.
+// Every valid key is >= key(-inf) = 0x007fffff, so 0 marks a slot outside the row.
+// A bf16 key keeps its 16 significant bits on top and zeros below (two of them share a register).
+template <typename T>
+RN_DEV uint32_t f2key(float x) {
+    if (x != x) x = -INFINITY;
+    x += 0.f;
+    const uint32_t b = __float_as_uint(x);
+    const uint32_t k = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+    return sizeof(T) == 2 ? k & 0xFFFF0000u : k;
+}
+template <typename T>
+RN_DEV float key2f(uint32_t k) {
+    const uint32_t b = k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu);
+    return __uint_as_float(sizeof(T) == 2 ? b & 0xFFFF0000u : b);
+}
+
+RN_DEV void ldvec(const bf16* p, float* f) { load8(p, f); }
+RN_DEV void ldvec(const float* p, float* f) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] = v[i];
+}
+
+// A thread's view of its row.  Slot s = (round · 1024 + thread) · VEC + q holds row index s - off,
+// where off (< VEC) is how far the row start lies past a 16-byte boundary: vectors that lie inside
+// the row are aligned whatever the row stride; the head and tail vectors are read element by element.
+template <typename T, int R>
+struct Row {
+    static constexpr int VEC = 16 / (int)sizeof(T), N = R > 0 ? R * VEC : 1;
+    static constexpr bool PACK = sizeof(T) == 2;  // two 16-bit keys per register
+    const T* row;
+    int V, off, rounds;
+    float m, c2;  // e = exp2((x - m) · c2)
+    uint32_t keys[PACK ? (N + 1) / 2 : N];
+    float e[N];
+
+    RN_DEV uint32_t key(int n) const {
+        if constexpr (PACK) return (n & 1) ? keys[n / 2] & 0xFFFF0000u : keys[n / 2] << 16;
+        else return keys[n];
+    }
+    RN_DEV void set_keys(int j, const uint32_t* k) {
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) {
+            if constexpr (!PACK) keys[j * VEC + q] = k[q];
+            else if (q & 1) keys[(j * VEC + q) / 2] = k[q] | (k[q - 1] >> 16);
+        }
+    }
+
+    RN_DEV int index(int j, int q) const { return (j * SMP_T + (int)threadIdx.x) * VEC + q - off; }
+    RN_DEV float mass(uint32_t k) const {
+        if (k == 0) return 0.f;
+        const float x = key2f<T>(k);
+        return x == m ? 1.f : __builtin_amdgcn_exp2f((x - m) * c2);
+    }
+    RN_DEV void load_round(int j, uint32_t* k) const {
+        const int i0 = index(j, 0);
+        if (i0 >= 0 && i0 <= V - VEC) {
+            float f[VEC];
+            ldvec(row + i0, f);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) k[q] = f2key<T>(f[q]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) {
+                const int i = i0 + q;
+                k[q] = 0u;
+                if (i >= 0 && i < V) k[q] = f2key<T>((float)row[i]);
+            }
+        }
+    }
+    // f(index, key, e) for the slots of round jsel / of every round, in index order
+    template <class F>
+    RN_DEV void visit_round(int jsel, F&& f) const {
+        if constexpr (R > 0) {
+#pragma unroll
+            for (int j = 0; j < R; ++j)
+                if (j == jsel) {
+#pragma unroll
+                    for (int q = 0; q < VEC; ++q) f(index(j, q), key(j * VEC + q), e[j * VEC + q]);
+                }
+        } else {
+            uint32_t k[VEC];
+            load_round(jsel, k);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) f(index(jsel, q), k[q], mass(k[q]));
+        }
+    }
+    template <class F>
+    RN_DEV void visit(F&& f) const {
+        if constexpr (R > 0) {
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+#pragma unroll
+                for (int q = 0; q < VEC; ++q) f(index(j, q), key(j * VEC + q), e[j * VEC + q]);
+            }
+        } else {
+            for (int j = 0; j < rounds; ++j) visit_round(j, f);
+        }
+    }
+};
+
+// Block-wide reduce, the result in every thread: xor butterfly, then the 16 wave partials in order
+// (a fixed tree).  Two LDS buffers used in turn, so one barrier per reduce is enough: a wave can
+// only write a buffer again after every wave has passed the barrier of the reduce in between.
+struct Reducer {
+    unsigned long long (*buf)[SMP_W];
+    int par = 0;
+    template <typename V, class Op>
+    RN_DEV V operator()(V v, Op op) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
+        V* s = reinterpret_cast<V*>(buf[par]);
+        par ^= 1;
+        if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+        __syncthreads();
+        V t = s[0];
+#pragma unroll
+        for (int i = 1; i < SMP_W; ++i) t = op(t, s[i]);
+        return t;
+    }
+};
+
+template <typename T, int R>
+__global__ void __launch_bounds__(SMP_T) sample_k(const T* __restrict__ logits, long ld, int V, float temperature,
+                                                  int top_k, float top_p, const float* __restrict__ params,
+                                                  const float* __restrict__ u_in, const uint64_t* __restrict__ seed,
+                                                  int64_t* __restrict__ tokens, int* __restrict__ kept) {
+    constexpr int VEC = Row<T, R>::VEC;
+    constexpr int LOW_BIT = 32 - 8 * (int)sizeof(T);  // bf16 keys: the low 16 bits carry no order
+    __shared__ unsigned long long red[2][SMP_W];
+    __shared__ float wave_tot[SMP_W];
+    Reducer reduce{red};
+    const auto add = [](auto a, auto b) { return a + b; };
+    const auto mx = [](auto a, auto b) { return a > b ? a : b; };
+    const auto mn = [](auto a, auto b) { return a < b ? a : b; };
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+
+    Row<T, R> r;
+    r.row = logits + (long)b * ld;
+    r.V = V;
+    r.off = (int)((reinterpret_cast<uintptr_t>(r.row) / sizeof(T)) % VEC);
+    r.rounds = (V + r.off + SMP_T * VEC - 1) / (SMP_T * VEC);
+    r.m = 0.f;
+    r.c2 = 0.f;
+    if constexpr (R > 0) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            uint32_t k[VEC];
+            r.load_round(j, k);
+            r.set_keys(j, k);
+        }
+    }
+    if (params) {  // device settings override the host ones: one captured graph serves every setting
+        temperature = params[0];
+        const float kf = params[1];
+        top_k = kf >= 1.f && kf < 1073741824.f ? (int)kf : 0;
+        top_p = params[2];
+    }
+
+    // largest key, lowest index on ties (the thread visits its slots in index order)
+    uint32_t bk = 0;
+    int bi = 0;
+    r.visit([&](int i, uint32_t k, float) {
+        if (k > bk) {
+            bk = k;
+            bi = i;
+        }
+    });
+    const unsigned long long best = reduce(((unsigned long long)bk << 32) | (uint32_t)~bi, mx);
+    const uint32_t M = (uint32_t)(best >> 32);
+    int amax = (int)~(uint32_t)best;
+    amax = amax < 0 ? 0 : (amax >= V ? V - 1 : amax);
+    if (!(temperature > 0.f)) {  // greedy
+        if (tid == 0) {
+            tokens[b] = amax;
+            kept[b] = 1;
+        }
+        return;
+    }
+
+    // the masses first: the floats just loaded are still in registers
+    r.m = key2f<T>(M);
+    r.c2 = 1.4426950408889634f / temperature;
+    if constexpr (R > 0) {
+#pragma unroll
+        for (int n = 0; n < R * VEC; ++n) r.e[n] = r.mass(r.key(n));
+    }
+
+    // top-k: thr = the k-th largest key = the largest t with #{key >= t} >= k, one bit at a time
+    uint32_t thr = 0;
+    if (top_k >= 1 && top_k < V) {
+        // a lower bound first, from one key per thread: k thread maxima >= c are k keys >= c
+        uint32_t low = 0;
+        for (int bit = 31; bit >= LOW_BIT; --bit) {
+            const uint32_t c = low | (1u << bit);
+            if (c <= M && reduce((int)(bk >= c), add) >= top_k) low = c;
+        }
+        for (int bit = 31; bit >= LOW_BIT; --bit) {
+            const uint32_t c = thr | (1u << bit);
+            if (c > M) continue;  // nothing is that large
+            if (c <= low) {       // at least k are: no pass over the row
+                thr = c;
+                continue;
+            }
+            int n = 0;
+            r.visit([&](int, uint32_t k, float) { n += k >= c; });
+            if (reduce(n, add) >= top_k) thr = c;
+        }
+    }
+
+    // top-p over the top-k set: the largest t whose mass of keys >= t reaches top_p · Z; a key >= t
+    // then has less than top_p of the mass strictly above it.  The largest key always stays.
+    if (top_p < 1.f) {
+        float z = 0.f;
+        r.visit([&](int, uint32_t k, float e) { z += k >= thr ? e : 0.f; });
+        const float need = top_p * reduce(z, add);
+        uint32_t t = M;
+        if (need > 0.f) {
+            t = 0;
+            for (int bit = 31; bit >= LOW_BIT; --bit) {
+                const uint32_t c = t | (1u << bit);
+                if (c > M) continue;
+                if (c <= thr) {  // the whole top-k set: its mass is Z
+                    t = c;
+                    continue;
+                }
+                const uint32_t cc = c;
+                    float q = 0.f;
+                r.visit([&](int, uint32_t k, float e) { q += k >= cc ? e : 0.f; });
+                if (reduce(q, add) >= need) t = c;
+            }
+        }
+        thr = t > thr ? t : thr;
+    }
+    thr = thr < M ? thr : M;
+
+    // level 1: per-round masses of the kept set, Z their sum in round order
+    int cnt = 0;
+    r.visit([&](int, uint32_t k, float) { cnt += k != 0 && k >= thr; });
+    cnt = reduce(cnt, add);
+    const auto round_sum = [&](int j) {
+        float w = 0.f;
+        r.visit_round(j, [&](int, uint32_t k, float e) { w += k >= thr ? e : 0.f; });
+        return reduce(w, add);
+    };
+    float Z = 0.f;
+    for (int j = 0; j < r.rounds; ++j) Z += round_sum(j);
+    float u = u_in ? u_in[b] : hash_uniform(*seed, (uint64_t)b);
+    u = u >= 0.f ? (u < 1.f ? u : 0.99999994f) : 0.f;
+    float target = u * Z;
+    int jsel = -1, jlast = -1;
+    float Psel = 0.f, Plast = 0.f, P = 0.f;
+    for (int j = 0; j < r.rounds; ++j) {
+        const float S = round_sum(j);  // the same tree as above: the same value
+        if (S > 0.f) {
+            jlast = j;
+            Plast = P;
+            if (jsel < 0 && P + S > target) {
+                jsel = j;
+                Psel = P;
+            }
+        }
+        P += S;
+    }
+    if (jlast < 0) {  // no mass at all (not reachable for finite settings): the argmax
+        if (tid == 0) {
+            tokens[b] = amax;
+            kept[b] = cnt;
+        }
+        return;
+    }
+    if (jsel < 0) {  // rounding left none: the last kept token of non-zero mass
+        jsel = jlast;
+        Psel = Plast;
+        target = INFINITY;
+    }
+
+    // level 2: inclusive scan of the threads' masses inside the hit round
+    float w = 0.f;
+    r.visit_round(jsel, [&](int, uint32_t k, float e) { w += k >= thr ? e : 0.f; });
+    float incl = w;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    float excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.f;
+    if (lane == 63) wave_tot[wid] = incl;
+    __syncthreads();
+    float base = Psel;
+    for (int i = 0; i < wid; ++i) base += wave_tot[i];
+    const int hit = w > 0.f && base + incl > target ? tid : SMP_T;
+    int tsel = reduce(hit, mn);
+    const int tlast = reduce(w > 0.f ? tid : -1, mx);
+    if (tsel == SMP_T) {
+        tsel = tlast;
+        target = INFINITY;
+    }
+
+    // level 3: the owning thread walks its vector
+    if (tid == tsel) {
+        float c = base + excl;
+        int tok = -1, last = -1;
+        r.visit_round(jsel, [&](int i, uint32_t k, float e) {
+            if (k >= thr && e > 0.f) {
+                c += e;
+                last = i;
+                if (tok < 0 && c > target) tok = i;
+            }
+        });
+        if (tok < 0) tok = last;
+        if (tok < 0 || tok >= V) tok = amax;
+        tokens[b] = tok;
+        kept[b] = cnt;
+    }
+}
+
+template <typename T>
+int launch(const void* logits, long ld, int B, int V, float temperature, int top_k, float top_p, const float* params,
+           const float* u, const uint64_t* seed, int64_t* tokens, int* kept, hipStream_t st) {
+    constexpr int VEC = 16 / (int)sizeof(T), PER = SMP_T * VEC;  // slots per round
+    constexpr int RFULL = 56 / VEC;                              // 56 values per thread in registers
+    const long slots = (long)V + VEC - 1;                        // the row start may sit VEC - 1 into a vector
+#define RN_SAMPLE(R_) \
+    sample_k<T, R_><<<B, SMP_T, 0, st>>>((const T*)logits, ld, V, temperature, top_k, top_p, params, u, seed, tokens, kept)
+    if (slots <= PER) RN_SAMPLE(1);
+    else if (slots <= (long)RFULL * PER) RN_SAMPLE(RFULL);
+    else RN_SAMPLE(0);
+#undef RN_SAMPLE
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
+// logits (B, V) bf16 / fp32 with row stride ld >= V; exactly one of u (B fp32 in [0, 1)) and seed
+// (row b draws hash_uniform(*seed, b)); params: 3 fp32 on the device (temperature, top_k, top_p)
+// overriding the host values, or null.  tokens (B) int64, kept (B) int32.
+extern "C" int rn_sample_logits(const void* logits, int is_bf16, long ld, int B, int V, float temperature, int top_k,
+                                float top_p, const float* params, const float* u, const uint64_t* seed,
+                                int64_t* tokens, int* kept, hipStream_t st) {
+    if (B < 1 || V < 1 || V > (1 << 30) || ld < V || (u == nullptr) == (seed == nullptr)) return 1;
+    return is_bf16 ? launch<bf16>(logits, ld, B, V, temperature, top_k, top_p, params, u, seed, tokens, kept, st)
+                   : launch<float>(logits, ld, B, V, temperature, top_k, top_p, params, u, seed, tokens, kept, st);
+}

@@ -13,6 +13,7 @@ import weakref
 import torch
 
 from .. import ops
+from ..ops import rng
 
 
 class KVCache:
@@ -188,16 +189,20 @@ DECODE_EOS_CHECK = 8  # ragged generate: "has every row finished?" is asked of t
 
 class _GraphRegistry(dict):
     """One model's captured decode steps kept across ``generate`` calls, least recently used first:
-    (batch, cache length, dtype, device, parameter storage[, "ragged" for the per-sequence step]) →
-    (cache, graph, token buffer, logits), so a serving loop captures once per (batch, length bucket).
+    (batch, cache length, dtype, device, parameter storage[, "ragged" for the per-sequence step]
+    [, "sampler" for a step captured together with the native sampler]) → (cache, graph, token buffer,
+    logits), so a serving loop captures once per (batch, length bucket).  A sampler entry holds the
+    sampled tokens (B, 1) in place of the logits, then the device tensor its settings are read from:
+    one graph whatever the temperature / top_k / top_p.
     At most DECODE_GRAPHS_MAX (REPLICANN_DECODE_GRAPHS, default 4) are kept; each holds its KV cache."""
 
-    def lookup(self, model, B, L, ragged, use):
+    def lookup(self, model, B, L, ragged, use, sampler=False):
         """(key, its stored entry — now the most recently used — or None).  The parameters' storage
         is part of the key: a graph reads them by address, so entries captured before a parameter was
         re-assigned (p.data = ...) are dropped here, whether or not this call will ``use`` a graph."""
         sig = tuple(p.data_ptr() for p in model.parameters())
         key = (B, L, model.wte.dtype, model.wte.device, sig) + (("ragged",) if ragged else ())
+        key += ("sampler",) if sampler else ()
         for k in [k for k in self if k[4] != sig]:
             del self[k]
         entry = self.pop(key, None) if use else None
@@ -218,63 +223,121 @@ def registry(model):
     return _REGISTRIES.setdefault(model, _GraphRegistry())
 
 
-def capture_step(model, cache, B):
+def sampler_params(temperature, top_k, top_p, device=None):
+    """(temperature, top_k, top_p) as the 3 fp32 values ``ops.sample_logits(params=...)`` reads (0 / 1: filter off)."""
+    return torch.tensor([temperature, top_k or 0, 1.0 if top_p is None else top_p], dtype=torch.float32, device=device)
+
+
+def _sampled_step(model, tok, cache, params):
+    """The one-token step followed by the native sampler on a fresh device seed: (B, 1) token ids."""
+    logits = model._device_position_step(tok, cache)
+    return ops.sample_logits(logits, params=params, seed_buf=rng.next_seed(logits.device))[0]
+
+
+def capture_step(model, cache, B, sampler=None):
     """Record the one-token decode step as a hipGraph (after one eager warm-up that tunes the
-    decode GEMM shapes); the caller writes the next token into ``tok`` and replays."""
+    decode GEMM shapes); the caller writes the next token into ``tok`` and replays.
+
+    ``sampler`` (host (temperature, top_k, top_p) to start from): the step and the native sampler are
+    recorded together — after the LM head the graph draws a device seed (``ops.rng``) and samples into
+    a static (B, 1) token buffer, its settings read from a device tensor; returns (graph, tok, tokens,
+    params).  The ``ops.rng`` states are restored around the warm-up and the capture: capturing
+    consumes no draws, so a capturing call and a replaying one started from the same state agree."""
     dev = model.wte.device
     tok = torch.zeros(B, 1, dtype=torch.long, device=dev)
     if not cache.device_pos:  # uniform: the prefill ran in host mode (ragged: it left per-sequence mode)
         cache.to_device_position()
+    params = None if sampler is None else sampler_params(*sampler, device=dev)
+    step = model._device_position_step if sampler is None else (lambda t, c: _sampled_step(model, t, c, params))
+    seeds = [(st, st.clone()) for st in rng.state_tensors(dev if sampler is not None else None)]
+
+    def restore():
+        cache.restore(snap)
+        for st, saved in seeds:
+            st.copy_(saved)
+
     snap = cache.snapshot()
     side = torch.cuda.Stream(dev)
     side.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(side):
-        model._device_position_step(tok, cache)
+        step(tok, cache)
     torch.cuda.current_stream(dev).wait_stream(side)
-    cache.restore(snap)
+    restore()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        out = model._device_position_step(tok, cache)
-    cache.restore(snap)
-    return graph, tok, out
+        out = step(tok, cache)
+    restore()
+    return (graph, tok, out) if sampler is None else (graph, tok, out, params)
 
 
 class _StepDriver:
     """One ``generate`` call's cache and one-token step.  With ``graph``, an earlier call's cache and
     captured step of the same key are reused; failing that the first ``step`` captures (and stores) one."""
 
-    def __init__(self, model, B, length, ragged, graph):
+    def __init__(self, model, B, length, ragged, graph, sampling, native):
         c = model.config
         if graph or ragged:  # one captured step (and cache) serves every length of a bucket
             length = min(c.block_size, -(-length // DECODE_LEN_BUCKET) * DECODE_LEN_BUCKET)
         self.model, self.B, self.graph, self.graphs = model, B, graph, registry(model)
-        self.key, self.entry = self.graphs.lookup(model, B, length, ragged, graph)
+        # sampling: (temperature, top_k, generator, top_p); native: ops.sample_logits instead of _sample
+        self.sampling, self.native = sampling, native
+        self.fused = native and graph  # the sampler is part of the captured step
+        self.settings_sent = False  # fused: has this call written its settings into the graph's tensor?
+        self.key, self.entry = self.graphs.lookup(model, B, length, ragged, graph, sampler=self.fused)
         self.cache = KVCache(c.n_layer, length) if self.entry is None else self.entry[0]
         self.cache.reset()
 
     def step(self, tok):
-        """Logits (B, vocab) after appending ``tok`` (B, 1); a replay returns its static buffer."""
+        """Logits (B, vocab) after appending ``tok`` (B, 1); a replay returns its static buffer (of a
+        step captured with the sampler: the sampled tokens (B, 1))."""
         if not self.graph:
             return self.model._device_position_step(tok, self.cache)
         if self.entry is None:
             self.graphs.make_room()  # before the capture allocates
-            self.entry = self.graphs[self.key] = (self.cache, *self.model._capture_decode(self.cache, self.B))
+            t, k, _, p = self.sampling
+            captured = self.model._capture_decode(self.cache, self.B, *([(t, k, p)] if self.fused else []))
+            self.entry = self.graphs[self.key] = (self.cache, *captured)
+            self.settings_sent = True  # a new sampler entry starts from this call's settings
         elif not self.cache.device_pos:  # a reused uniform cache: its prefill ran in host mode
             self.cache.to_device_position()
-        _, graph, buf, out = self.entry
+        _, graph, buf, out = self.entry[:4]
+        if self.fused and not self.settings_sent:  # a stored graph: this call's settings, once
+            t, k, _, p = self.sampling
+            self.entry[4].copy_(sampler_params(t, k, p))
+            self.settings_sent = True
         buf.copy_(tok)
         graph.replay()
         return out
 
+    def pick(self, logits):
+        """(B, vocab) logits → (B, 1) token ids by this call's sampler; what a step captured with the
+        sampler returned is the tokens already: a copy (the next replay rewrites that static buffer)."""
+        if logits.dtype == torch.long:
+            return logits.clone()
+        temperature, top_k, generator, top_p = self.sampling
+        if not self.native:
+            return _sample(logits.float(), *self.sampling)
+        if not logits.is_cuda:  # the reference math of ops.sample_logits on uniforms from the host generator
+            u = torch.rand(logits.shape[0], generator=generator)
+            return ops.sample_logits(logits.float(), temperature, top_k, top_p, u=u)[0]
+        return ops.sample_logits(logits, temperature, top_k, top_p, seed_buf=rng.next_seed(logits.device))[0]
+
 
 @torch.no_grad()
 def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=None, generator=None, graph=None,
-             prompt_lens=None, eos_token_id=None, pad_token_id=None):
+             prompt_lens=None, eos_token_id=None, pad_token_id=None, sampler="torch"):
     """Autoregressive sampling with a KV cache: ``idx`` (B, T0) prompt → (B, T0 + max_new_tokens).
     ``temperature`` 0 = greedy; ``top_k`` / ``top_p`` restrict sampling.  One prefill pass over the prompt, then one-token steps whose
     attention reads the cached keys / values (no recomputation of the prefix).  ``graph``
     (default: on for GPU models): the one-token step is captured once as a hipGraph and replayed
     (per-step values live on the device), so a step costs its kernels, not ~130 host launches.
+
+    ``sampler``: ``"torch"`` (default) samples with ATen ops on the host's ``generator`` after every
+    step; ``"native"`` with the fused ``ops.sample_logits`` kernel (its semantics differ only inside
+    tie groups: whole groups are kept).  On a GPU model its randomness is the device seed stream of
+    ``ops.rng`` (``ops.rng.manual_seed``; a ``generator`` is an error) and, with ``graph``, the sampler
+    is captured with the step: a generation is a prefill, one sample and replays.  On a CPU model the
+    uniforms come from ``generator``.
 
     Ragged batches / stopping (either of ``prompt_lens``, ``eos_token_id`` given): ``idx`` is
     right-padded, row b's prompt is ``idx[b, :prompt_lens[b]]`` (default: all of it) and whatever the
@@ -287,6 +350,14 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     ragged = prompt_lens is not None or eos_token_id is not None
     if top_p is not None and not 0.0 < top_p <= 1.0:
         raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    if sampler not in ("torch", "native"):
+        raise ValueError(f"sampler must be 'torch' or 'native', got {sampler!r}")
+    native = sampler == "native"
+    if native and generator is not None and model.wte.is_cuda:
+        raise ValueError("sampler='native' on a GPU model draws from the device seed stream "
+                         "(ops.rng.manual_seed), not from a torch.Generator")
+    if native and (temperature < 0 or (top_k is not None and top_k < 0)):
+        raise ValueError(f"sampler='native' needs temperature >= 0 and top_k >= 0, got {temperature}, {top_k}")
     plens = [T0] * B if prompt_lens is None else host_lens("prompt_lens", prompt_lens, B, T0)
     Tm = max(plens)
     if ragged and max_new_tokens < 1:
@@ -297,14 +368,14 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     was_training = model.training
     model.eval()
     try:
-        driver = _StepDriver(model, B, Tm + max_new_tokens, ragged, use_graph)
-        sampling = (temperature, top_k, generator, top_p)
+        driver = _StepDriver(model, B, Tm + max_new_tokens, ragged, use_graph,
+                             (temperature, top_k, generator, top_p), native)
         if ragged:
-            return _ragged_loop(driver, idx[:, :Tm], plens, max_new_tokens, eos_token_id, pad_token_id, sampling)
+            return _ragged_loop(driver, idx[:, :Tm], plens, max_new_tokens, eos_token_id, pad_token_id)
         logits = model.decode_step(idx, driver.cache)
         out = [idx]
         for i in range(max_new_tokens):
-            out.append(_sample(logits.float(), *sampling))
+            out.append(driver.pick(logits))
             if i + 1 < max_new_tokens:
                 logits = driver.step(out[-1])
         return torch.cat(out, 1)
@@ -312,7 +383,7 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
         model.train(was_training)
 
 
-def _ragged_loop(driver, idx, plens, max_new_tokens, eos, pad, sampling):
+def _ragged_loop(driver, idx, plens, max_new_tokens, eos, pad):
     (B, Tm), dev = idx.shape, idx.device  # idx: the prompts cut to the longest one
     if pad is None:
         pad = eos if eos is not None else 0
@@ -324,7 +395,7 @@ def _ragged_loop(driver, idx, plens, max_new_tokens, eos, pad, sampling):
     finished = torch.zeros(B, dtype=torch.bool, device=dev)
     logits = driver.model.decode_step(idx, driver.cache, lens=plens)
     for i in range(max_new_tokens):
-        nxt = _sample(logits.float(), *sampling)
+        nxt = driver.pick(logits)
         nxt = torch.where(finished.unsqueeze(1), torch.full_like(nxt, pad), nxt)  # finished rows emit pad
         tokens.scatter_(1, lens.unsqueeze(1), nxt)
         lens += ~finished

@@ -195,8 +195,8 @@ class GPT2(nn.Module):
         """The one-token step ``tok`` (B, 1) → (B, vocab) logits that ``generate`` runs or captures."""
         return self.decode_step(tok, cache)
 
-    def _capture_decode(self, cache, B):
-        return decoding.capture_step(self, cache, B)
+    def _capture_decode(self, cache, B, sampler=None):
+        return decoding.capture_step(self, cache, B, sampler)
 
     # generation itself (the cache, the sampling loops, the captured-step registry): models/decoding.py
     generate = decoding.generate

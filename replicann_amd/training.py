@@ -500,6 +500,9 @@ def generate_main(argv=None):
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-k", type=int, default=None)
     ap.add_argument("--top-p", type=float, default=None)
+    ap.add_argument("--sampler", choices=("torch", "native"), default="torch",
+                    help="native: the fused sampling kernel, captured with the decode step on a GPU (seeded by --seed "
+                         "through the device seed stream)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default=None)
     ap.add_argument("--model-kwargs", type=json.loads, default={})
@@ -518,6 +521,10 @@ def generate_main(argv=None):
         load_committed(a.model)
         model = model.to(torch.bfloat16)
     gen = torch.Generator(device=dev).manual_seed(a.seed)
+    if a.sampler == "native" and dev.type == "cuda":  # the device seed stream takes the generator's place
+        from .ops import rng
+        rng.manual_seed(a.seed)
+        gen = None
     prompts = [[int(t) for t in p.split(",")] for p in a.prompt or []]
     if len(prompts) > 1 or a.eos is not None:  # ragged batch and / or stopping
         if not prompts:
@@ -527,7 +534,7 @@ def generate_main(argv=None):
         t0 = time.perf_counter()
         rows = model.generate_batch([torch.tensor(p, dtype=torch.long) for p in prompts], a.new,
                                     temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, generator=gen,
-                                    eos_token_id=a.eos, pad_token_id=a.pad)
+                                    eos_token_id=a.eos, pad_token_id=a.pad, sampler=a.sampler)
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
@@ -542,7 +549,8 @@ def generate_main(argv=None):
     else:
         ids = torch.randint(0, model.config.vocab_size, (a.batch_size, a.prompt_len))
     t0 = time.perf_counter()
-    out = model.generate(ids.to(dev), a.new, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, generator=gen)
+    out = model.generate(ids.to(dev), a.new, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, generator=gen,
+                         sampler=a.sampler)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0

@@ -14,6 +14,14 @@ spread evenly over 16 .. 512.  One JSON line per timed run and a summary line wi
 the (b) / (a) ratio.
 
     python scripts/decode_bench.py --ragged
+
+``--sample``: sampled decoding (temperature 0.8, top_k 50, top_p 0.95) with the default sampler
+(``sampler="torch"``: ATen ops after every replay) against the fused one captured with the step
+(``sampler="native"``), the greedy captured step beside them, at batch 1, 16 and 64: the three
+alternated in one process, three rounds.  One JSON line per timed run, then per batch a summary line
+with the median ms per decode step of each and the torch / native ratio.
+
+    python scripts/decode_bench.py --sample
 """
 
 import argparse
@@ -80,6 +88,40 @@ def ragged(m, model, B=64, prompt=128, new=128, rounds=3):
                       "ragged_equal_over_uniform": round(med[b] / med[a], 4)}), flush=True)
 
 
+def sample(m, model, batches, prompt=128, new=128, rounds=3):
+    """sampler="torch" against sampler="native" (and greedy), alternated per round, per batch size."""
+    from replicann_amd.models.blocks import KVCache
+    from replicann_amd.ops import rng
+    dev = torch.device("cuda")
+    rng.manual_seed(0)
+    sampled = dict(temperature=0.8, top_k=50, top_p=0.95, graph=True)
+    for B in batches:
+        idx = torch.randint(0, m.config.vocab_size, (B, prompt), device=dev)
+        gen = torch.Generator(device=dev).manual_seed(0)
+        cases = {
+            "greedy": lambda: m.generate(idx, new, temperature=0, graph=True),
+            "torch": lambda: m.generate(idx, new, sampler="torch", generator=gen, **sampled),
+            "native": lambda: m.generate(idx, new, sampler="native", **sampled),
+        }
+        for fn in cases.values():  # warm-up: GEMM tuning, graph capture
+            fn()
+        prefill = min(_timed(lambda: m.decode_step(idx, KVCache(m.config.n_layer, prompt + new)))[0] for _ in range(2))
+        steps = {k: [] for k in cases}
+        for r in range(rounds):
+            for name, fn in cases.items():
+                total, _ = _timed(fn)
+                ms = (total - prefill) / (new - 1) * 1e3
+                steps[name].append(ms)
+                print(json.dumps({"model": model, "batch": B, "prompt": prompt, "new_tokens": new, "sampler": name,
+                                  "round": r, "prefill_ms": round(prefill * 1e3, 3), "decode_ms_per_step": round(ms, 4),
+                                  "generated_tokens_per_s": round(B * new / total, 1)}), flush=True)
+        med = {k: sorted(v)[len(v) // 2] for k, v in steps.items()}
+        print(json.dumps({"summary": "median decode ms/step", "batch": B, **{k: round(v, 4) for k, v in med.items()},
+                          "sampling_cost_torch_ms": round(med["torch"] - med["greedy"], 4),
+                          "sampling_cost_native_ms": round(med["native"] - med["greedy"], 4),
+                          "torch_over_native": round(med["torch"] / med["native"], 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2-small")
@@ -87,6 +129,7 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--ragged", action="store_true", help="uniform against ragged decode step (see above)")
+    ap.add_argument("--sample", action="store_true", help="sampler='torch' against sampler='native' (see above)")
     a = ap.parse_args()
     from replicann_amd import _ext
     from replicann_amd.models.blocks import KVCache
@@ -103,6 +146,8 @@ def main():
     m.eval()
     if a.ragged:
         return ragged(m, a.model, prompt=a.prompt, new=a.new)
+    if a.sample:
+        return sample(m, a.model, [int(b) for b in a.batches.split(",")], prompt=a.prompt, new=a.new)
     for B in [int(b) for b in a.batches.split(",")]:
         idx = torch.randint(0, m.config.vocab_size, (B, a.prompt), device=dev)
         prefill = None
