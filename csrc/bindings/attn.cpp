@@ -1,0 +1,249 @@
+// Attention and decoding bindings: attn_fwd and the backward forms, attn_decode, linear_kv, sample_logits
+// (kernels: attention*.hip, attention_decode.hip, gemm_skinny.hip, sampling.hip).  Not named attention.cpp:
+// the build keys its per-unit compiler flags by file stem, and those of attention.hip are for device code.
+#include "binding_util.h"
+#include "rn_api.h"
+
+namespace {
+
+// decode-step QKV projection with the K|V cache append fused into the epilogue (gemm_skinny.hip):
+// x (M, K), w (N, K), kv (M, L, 2, H, D) contiguous cache, pos: int64 device row index, 1 element
+// (shared by the batch) or M (one per batch row); a position outside [0, L) appends nothing
+Tensor linear_kv(const Tensor& x, const Tensor& w, const optional<Tensor>& bias, const Tensor& kv, const Tensor& pos) {
+    CHECK_CUDA(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(kv); GUARD(x);
+    TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && w.dim() == 2 && w.stride(1) == 1, "linear_kv: 2-D row-major operands");
+    const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
+    TORCH_CHECK(w.size(1) == K, "linear_kv: inner dims differ");
+    TORCH_CHECK(kv.dim() == 5 && kv.is_contiguous() && kv.size(0) == M && kv.size(2) == 2, "linear_kv: kv must be (M, L, 2, H, D)");
+    const int64_t kvw = kv.size(2) * kv.size(3) * kv.size(4);
+    TORCH_CHECK(kvw <= N, "linear_kv: cache row wider than the projection");
+    TORCH_CHECK(pos.scalar_type() == at::kLong && (pos.numel() == 1 || pos.numel() == M) && pos.is_contiguous() &&
+                    pos.is_cuda(),
+                "linear_kv: pos must be 1 or M contiguous int64 values on the device");
+    TORCH_CHECK(kv.size(1) >= 1 && kv.size(1) <= (int64_t)1 << 30,"linear_kv: cache length out of range");
+    TORCH_CHECK(w.device() == x.device() && kv.device() == x.device() && pos.device() == x.device() &&
+                    (!has(bias) || bias->device() == x.device()),
+                "linear_kv: x, w, bias, kv and pos must be on one device");
+    if (has(bias)) { CHECK_BF16(*bias); TORCH_CHECK(bias->numel() == N && bias->is_contiguous()); }
+    Tensor c = at::empty({M, N}, x.options());
+    const int rc = rn_gemm_skinny_kv(x.data_ptr(), w.data_ptr(), optr(bias), c.data_ptr(), (int)M, (int)N, (int)K,
+                                     x.stride(0), w.stride(0), c.stride(0), kv.data_ptr(), pos.data_ptr<int64_t>(),
+                                     pos.numel() == 1 ? 0 : 1, (int)kv.size(1), kv.stride(0), kv.stride(1),
+                                     (int)(N - kvw), cur_stream());
+    TORCH_CHECK(rc == 0, "linear_kv: unsupported shape M=", M, " K=", K, " (M <= 64, K % 8 == 0)");
+    return c;
+}
+
+// one-query attention over a KV cache (decode step, attention_decode.hip): q (B, 1, H, 64), k / v
+// (B, Tk, H, 64) strided views, mask: Tk fp32 additive shared by the batch (or none); lens (instead
+// of a mask): (B,) int32 / int64 key counts, batch row b attends to keys 0 .. lens[b]-1 only
+Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, double scale,
+                   const optional<Tensor>& lens) {
+    CHECK_BF16(q); CHECK_BF16(k); CHECK_BF16(v); GUARD(q);
+    TORCH_CHECK(q.dim() == 4 && q.size(1) == 1, "attn_decode: one query per (batch, head)");
+    const int B = q.size(0), H = q.size(2), D = q.size(3), Tk = k.size(1);
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4, "attn_decode: k / v must be (B, Tk, H, D)");
+    TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(2) == H && v.size(2) == H && v.size(1) == Tk &&
+                    k.size(3) == D && v.size(3) == D,
+                "attn_decode: shape mismatch (q ", q.sizes(), ", k ", k.sizes(), ", v ", v.sizes(), ")");
+    TORCH_CHECK(k.device() == q.device() && v.device() == q.device(), "attn_decode: q, k, v on different devices");
+    // the kernel reads 16-B vectors: base pointers and every non-unit stride 16-B aligned
+    for (const Tensor* t : {&q, &k, &v})
+        TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0 && t->stride(3) == 1,
+                    "attn_decode: q / k / v need a 16-byte aligned base and a contiguous head dimension");
+    if (has(mask))
+        TORCH_CHECK(mask->scalar_type() == at::kFloat && mask->is_contiguous() && mask->numel() == Tk &&
+                        mask->device() == q.device(),
+                    "attn_decode: mask must be Tk contiguous fp32 values on q's device");
+    const bool has_lens = has(lens);
+    if (has_lens) {
+        TORCH_CHECK(!has(mask), "attn_decode: lens cannot be combined with a mask");
+        TORCH_CHECK(lens->dim() == 1 && lens->size(0) == B && lens->is_contiguous(),
+                    "attn_decode: lens must be a contiguous (B,) tensor, got ", lens->sizes());
+        TORCH_CHECK(lens->scalar_type() == at::kInt || lens->scalar_type() == at::kLong,
+                    "attn_decode: lens must be int32 or int64, got ", lens->scalar_type());
+        TORCH_CHECK(lens->device() == q.device(), "attn_decode: lens must be on q's device");
+    }
+    Tensor o = at::empty({B, 1, H, D}, q.options());
+    std::vector<long> s;
+    std::vector<long> t;
+    strides_bth(q, t); s.push_back(t[0]); s.push_back(t[2]); t.clear();
+    strides_bth(k, t); s.insert(s.end(), t.begin(), t.end()); t.clear();
+    strides_bth(v, t); s.insert(s.end(), t.begin(), t.end()); t.clear();
+    strides_bth(o, t); s.push_back(t[0]); s.push_back(t[2]);
+    const int rc = rn_attn_decode(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                  has(mask) ? mask->data_ptr<float>() : nullptr,
+                                  has_lens ? lens->data_ptr() : nullptr,
+                                  has_lens && lens->scalar_type() == at::kLong ? 1 : 0, o.data_ptr(), B, H, Tk, D,
+                                  s.data(), (float)scale, cur_stream());
+    TORCH_CHECK(rc == 0, "attn_decode: unsupported shape D=", D, " Tk=", Tk, " (D == 64, Tk <= 1024)");
+    return o;
+}
+
+// fused token sampler (sampling.hip): logits (B, V) bf16 / fp32 with a unit column stride and a row
+// stride >= V (a column slice of a wider buffer is fine) -> (tokens (B, 1) int64, kept (B,) int32).
+// Exactly one of u ((B,) fp32 uniforms) and seed_buf (row b draws hash_uniform(seed, b)); params: 3
+// fp32 on the device (temperature, top_k, top_p) that override the host values, so that one captured
+// graph serves every setting.
+std::tuple<Tensor, Tensor> sample_logits(const Tensor& logits, double temperature, int64_t top_k, double top_p,
+                                         const optional<Tensor>& u, const optional<Tensor>& seed_buf,
+                                         const optional<Tensor>& params) {
+    CHECK_CUDA(logits); GUARD(logits);
+    TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat,
+                "sample_logits: logits must be bfloat16 or float32, got ", logits.scalar_type());
+    TORCH_CHECK(logits.dim() == 2 && logits.size(1) >= 1, "sample_logits: logits must be (B, V >= 1), got ",
+                logits.sizes());
+    const int64_t B = logits.size(0), V = logits.size(1);
+    TORCH_CHECK(V <= (1 << 30), "sample_logits: V = ", V, " exceeds 2^30");
+    TORCH_CHECK(logits.stride(1) == 1 && (B == 1 || logits.stride(0) >= V),
+                "sample_logits: logits need a unit column stride and a row stride >= V, got strides ",
+                logits.strides());
+    TORCH_CHECK(temperature >= 0.0 && temperature < INFINITY, "sample_logits: temperature must be finite and >= 0, got ",
+                temperature);
+    TORCH_CHECK(top_k >= 0, "sample_logits: top_k must be >= 0 (0 = off), got ", top_k);
+    TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "sample_logits: top_p must be in (0, 1], got ", top_p);
+    const bool has_u = has(u), has_seed = has(seed_buf);
+    TORCH_CHECK(has_u != has_seed, "sample_logits: exactly one of u and seed_buf must be given");
+    if (has_u)
+        TORCH_CHECK(u->scalar_type() == at::kFloat && u->dim() == 1 && u->size(0) == B && u->is_contiguous() &&
+                        u->device() == logits.device(),
+                    "sample_logits: u must be a contiguous (B,) float32 tensor on the logits' device");
+    const uint64_t* seed = seed_ptr(seed_buf);
+    if (has_seed) TORCH_CHECK(seed_buf->device() == logits.device(), "sample_logits: seed_buf must be on the logits' device");
+    const bool has_params = has(params);
+    if (has_params)
+        TORCH_CHECK(params->scalar_type() == at::kFloat && params->numel() == 3 && params->is_contiguous() &&
+                        params->device() == logits.device(),
+                    "sample_logits: params must be 3 contiguous float32 values (temperature, top_k, top_p) on the "
+                    "logits' device");
+    Tensor tokens = at::empty({B, 1}, logits.options().dtype(at::kLong));
+    Tensor kept = at::empty({B}, logits.options().dtype(at::kInt));
+    if (B == 0) return {tokens, kept};
+    const int rc = rn_sample_logits(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, B == 1 ? V : logits.stride(0),
+                                    (int)B, (int)V, (float)temperature, (int)std::min<int64_t>(top_k, 1 << 30),
+                                    (float)top_p, has_params ? params->data_ptr<float>() : nullptr,
+                                    has_u ? u->data_ptr<float>() : nullptr, seed, tokens.data_ptr<int64_t>(),
+                                    kept.data_ptr<int>(), cur_stream());
+    TORCH_CHECK(rc == 0, "sample_logits: unsupported arguments (B=", B, ", V=", V, ")");
+    return {tokens, kept};
+}
+
+std::tuple<Tensor, Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& bias,
+                                    double scale, bool causal, double p, int64_t seed,
+                                    const optional<Tensor>& seed_buf) {
+    CHECK_BF16(q); CHECK_BF16(k); CHECK_BF16(v); GUARD(q);
+    const int B = q.size(0), Tq = q.size(1), H = q.size(2), D = q.size(3), Tk = k.size(1);
+    Tensor o = at::empty({B, Tq, H, D}, q.options());
+    Tensor lse = at::empty({B, H, Tq}, q.options().dtype(at::kFloat));
+    std::vector<long> s;
+    strides_bth(q, s); strides_bth(k, s); strides_bth(v, s); strides_bth(o, s);
+    int bias_b = 1;
+    if (has(bias)) {
+        TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->dim() == 3 && bias->is_contiguous());
+        bias_b = bias->size(0);
+    }
+    if (B * H * Tq == 0) return {o, lse};
+    int rc = rn_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                         has(bias) ? bias->data_ptr<float>() : nullptr, bias_b, s.data(), B, H, Tq, Tk, D,
+                         (float)scale, causal, (float)p, (uint64_t)seed, seed_ptr(seed_buf), cur_stream());
+    TORCH_CHECK(rc == 0, "attention: unsupported shape or failed launch (", rc, ") D=", D, " Tk=", Tk);
+    return {o, lse};
+}
+// q8 / q8st / q8_only: see AttnArgs (attention_common.h); returns false (nothing launched) when the kernels
+// cannot emit e5m2 for this shape
+bool attn_bwd_impl(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
+                   const Tensor& lse, const optional<Tensor>& bias, double scale, bool causal, double p, int64_t seed,
+                   const Tensor& dq, const Tensor& dk, const Tensor& dv, const optional<Tensor>& qkv_bias_grad = {},
+                   const optional<Tensor>& seed_buf = {}, void* q8 = nullptr, float* q8st = nullptr, bool q8_only = false) {
+    GUARD(q);
+    const int B = q.size(0), Tq = q.size(1), H = q.size(2), D = q.size(3), Tk = k.size(1);
+    std::vector<long> s;
+    for (const Tensor* t : {&q, &k, &v, &o, &dout, &dq, &dk, &dv}) strides_bth(*t, s);
+    Tensor delta = at::empty({B, H, Tq}, q.options().dtype(at::kFloat));
+    int bias_b = has(bias) ? bias->size(0) : 1;
+    if (B * H * Tq == 0) return true;
+    // packed-QKV bias gradient: per-64-row-block column partials from the kernels, then one reduction
+    Tensor bsum;
+    const bool want_bg = has(qkv_bias_grad);
+    const int nblk = (Tq + 63) / 64;
+    if (want_bg) {
+        CHECK_BF16(*qkv_bias_grad);
+        TORCH_CHECK(qkv_bias_grad->numel() == 3L * H * D && qkv_bias_grad->is_contiguous() && rn_attn_is_fast(D) &&
+                    Tq == Tk, "qkv bias gradient: packed self-attention with head_dim 32, 64 or 128 only");
+        bsum = at::empty({(int64_t)B * nblk, 3L * H * D}, q.options().dtype(at::kFloat));
+    }
+    Tensor q8part = q8 ? at::empty({rn_attn_q8_part_floats(B, H, Tq, Tk)}, q.options().dtype(at::kFloat)) : Tensor();
+    int rc = rn_attn_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                         has(bias) ? bias->data_ptr<float>() : nullptr, bias_b, dq.data_ptr(), dk.data_ptr(),
+                         dv.data_ptr(), delta.data_ptr<float>(), s.data(), B, H, Tq, Tk, D, (float)scale, causal, (float)p,
+                         (uint64_t)seed, seed_ptr(seed_buf), want_bg ? bsum.data_ptr<float>() : nullptr, q8, q8st,
+                         q8_only ? 1 : 0, q8 ? q8part.data_ptr<float>() : nullptr, cur_stream());
+    if (rc == -3 && q8) return false;
+    TORCH_CHECK(rc == 0, "attention backward: unsupported shape or failed launch (", rc, ") D=", D);
+    if (want_bg) {
+        const int C = 3 * H * D;
+        Tensor tmp = at::empty({rn_colsum_ws(C)}, q.options().dtype(at::kFloat));
+        rn_colsum_f32(bsum.data_ptr<float>(), B * nblk, C, tmp.data_ptr<float>(), qkv_bias_grad->data_ptr(), 1,
+                      cur_stream());
+    }
+    return true;
+}
+std::tuple<Tensor, Tensor, Tensor> attn_bwd(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v,
+                                            const Tensor& o, const Tensor& lse, const optional<Tensor>& bias,
+                                            double scale, bool causal, double p, int64_t seed,
+                                            const optional<Tensor>& seed_buf) {
+    Tensor dq = at::empty(q.sizes(), q.options());
+    Tensor dk = at::empty(k.sizes(), k.options());
+    Tensor dv = at::empty(v.sizes(), v.options());
+    attn_bwd_impl(dout, q, k, v, o, lse, bias, scale, causal, p, seed, dq, dk, dv, {}, seed_buf);
+    return {dq, dk, dv};
+}
+void attn_bwd_out(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
+                  const Tensor& lse, const optional<Tensor>& bias, double scale, bool causal, double p, int64_t seed,
+                  const Tensor& dq, const Tensor& dk, const Tensor& dv, const optional<Tensor>& qkv_bias_grad,
+                  const optional<Tensor>& seed_buf) {
+    attn_bwd_impl(dout, q, k, v, o, lse, bias, scale, causal, p, seed, dq, dk, dv, qkv_bias_grad, seed_buf);
+}
+// the same with the packed dQKV also (q8_only: only) written as e5m2 into q8 (uint8, dQKV's shape) with the
+// delayed-scaling slot q8_state (rolled here); false = this shape cannot (nothing launched)
+bool attn_bwd_out_q8(const Tensor& dout, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
+                     const Tensor& lse, const optional<Tensor>& bias, double scale, bool causal, double p, int64_t seed,
+                     const Tensor& dq, const Tensor& dk, const Tensor& dv, const optional<Tensor>& qkv_bias_grad,
+                     const optional<Tensor>& seed_buf, const Tensor& q8, const Tensor& q8_state, bool q8_only) {
+    TORCH_CHECK(q8.scalar_type() == at::kByte && q8.is_cuda() && q8.device() == q.device(), "attn q8: uint8 on the device");
+    TORCH_CHECK(q8_state.scalar_type() == at::kFloat && q8_state.numel() >= 4 && q8_state.device() == q.device());
+    // the e5m2 image uses element offsets from dq: q8 is the byte twin of the packed dQKV dq / dk / dv view
+    TORCH_CHECK(q8.numel() == 3 * dq.numel() && dq.data_ptr() < dk.data_ptr() && dk.data_ptr() < dv.data_ptr(),
+                "attn q8: the e5m2 twin of a packed (B, T, 3, H, D) dQKV");
+    return attn_bwd_impl(dout, q, k, v, o, lse, bias, scale, causal, p, seed, dq, dk, dv, qkv_bias_grad, seed_buf,
+                         q8.data_ptr(), q8_state.data_ptr<float>(), q8_only);
+}
+
+}  // namespace
+
+TORCH_LIBRARY_FRAGMENT(replicann, m) {
+    m.def("attn_decode(Tensor q, Tensor k, Tensor v, Tensor? mask, float scale, Tensor? lens=None) -> Tensor");
+    m.def("linear_kv(Tensor x, Tensor w, Tensor? bias, Tensor(a!) kv, Tensor pos) -> Tensor");
+    m.def("sample_logits(Tensor logits, float temperature, int top_k, float top_p, Tensor? u, Tensor? seed_buf, "
+          "Tensor? params) -> (Tensor, Tensor)");
+    m.def("attn_fwd(Tensor q, Tensor k, Tensor v, Tensor? bias, float scale, bool causal, float p, int seed, "
+          "Tensor? seed_buf=None) -> (Tensor, Tensor)");
+    m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor? bias, float scale, "
+          "bool causal, float p, int seed, Tensor? seed_buf=None) -> (Tensor, Tensor, Tensor)");
+    m.def("attn_bwd_out(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor? bias, float scale, "
+          "bool causal, float p, int seed, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, "
+          "Tensor(d!)? qkv_bias_grad=None, Tensor? seed_buf=None) -> ()");
+    m.def("attn_bwd_out_q8(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor? bias, float scale, "
+          "bool causal, float p, int seed, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, "
+          "Tensor(d!)? qkv_bias_grad, Tensor? seed_buf, Tensor(e!) q8, Tensor(f!) q8_state, bool q8_only) -> bool");
+}
+
+TORCH_LIBRARY_IMPL(replicann, CUDA, m) {
+    m.impl("attn_decode", &attn_decode);
+    m.impl("linear_kv", &linear_kv);
+    m.impl("sample_logits", &sample_logits);
+    m.impl("attn_fwd", &attn_fwd);
+    m.impl("attn_bwd", &attn_bwd);
+    m.impl("attn_bwd_out", &attn_bwd_out);
+    m.impl("attn_bwd_out_q8", &attn_bwd_out_q8);
+}

@@ -43,8 +43,7 @@
 #include <thread>
 #include <vector>
 
-extern "C" void rn_comm_proxy(void* buf, long bytes, double volume_bytes, int wgs, double gbps, hipStream_t st);
-extern "C" void rn_cast_f32_bf16(const float* in, void* out, long n, hipStream_t st);
+#include "rn_api.h"
 
 namespace {
 

@@ -1046,3 +1046,28 @@ void launch_fp8_t(GemmArgs& a, hipStream_t st) {
 }
 
 }  // namespace rn_gemm_detail
+
+// Launch entry points of the GEMM units (C++ linkage), declared once: each is defined in the unit its
+// name says (gemm_cfg*.hip, gemm_pk_*.hip, gemm_pk_fp8.hip, gemm_w1.hip) and called from gemm_bf16.hip
+// and fp8.hip.  ak / bk: the operand is K-contiguous.  The int forms return 0, or -1 for what the
+// kernel does not take (nothing launched).
+void rn_gemm_launch_cfg0(rn_gemm_detail::GemmArgs& a, bool ak, bool bk, int act, hipStream_t st);
+void rn_gemm_launch_cfg1(rn_gemm_detail::GemmArgs& a, bool ak, bool bk, int act, hipStream_t st);
+void rn_gemm_launch_cfg2(rn_gemm_detail::GemmArgs& a, bool ak, bool bk, int act, hipStream_t st);
+void rn_gemm_launch_cfg3(rn_gemm_detail::GemmArgs& a, bool ak, bool bk, int act, hipStream_t st);
+void rn_gemm_launch_cfg4(rn_gemm_detail::GemmArgs& a, bool ak, bool bk, int act, hipStream_t st);
+void rn_gemm_launch_cfg5(rn_gemm_detail::GemmArgs& a, bool ak, bool bk, int act, hipStream_t st);
+void rn_gemm_launch_cfg6(rn_gemm_detail::GemmArgs& a, bool ak, bool bk, int act, hipStream_t st);
+void rn_gemm_launch_cfg8(rn_gemm_detail::GemmArgs& a, bool ak, bool bk, int act, hipStream_t st);
+void rn_gemm_launch_pk_tt(rn_gemm_detail::GemmArgs& a, int act, hipStream_t st);
+void rn_gemm_launch_pk_tf(rn_gemm_detail::GemmArgs& a, int act, hipStream_t st);
+void rn_gemm_launch_pk_ff(rn_gemm_detail::GemmArgs& a, int act, hipStream_t st);
+void rn_gemm_launch_pk_ft(rn_gemm_detail::GemmArgs& a, int act, hipStream_t st);
+void rn_gemm_launch_pk_fp8(rn_gemm_detail::GemmArgs& a, int act, hipStream_t st);
+void rn_gemm_launch_pk_fp8_wgrad(rn_gemm_detail::GemmArgs& a, int a_bf8, hipStream_t st);
+void rn_gemm_launch_pk_fp8_dgrad(rn_gemm_detail::GemmArgs& a, int a_bf8, hipStream_t st);
+int rn_gemm_launch_w1(rn_gemm_detail::GemmArgs& a, int fp8, int act, hipStream_t st, bool bmn);
+int rn_gemm_launch_w1_wgrad(rn_gemm_detail::GemmArgs& a, int fp8, int split, hipStream_t st);
+#ifdef REPLICANN_DEV
+int rn_gemm_launch_pk_dbg(rn_gemm_detail::GemmArgs& a, bool ak, bool bk, int dbg, hipStream_t st);  // dev builds only
+#endif

@@ -86,6 +86,7 @@
 #include <type_traits>
 
 #include "gemm_impl.h"
+#include "rn_api.h"
 
 namespace rn_gemm_detail {
 
@@ -920,10 +921,6 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
 //   communicator is active); the dynamic schedule (rn_gemm_set_sched, default on) takes a counter
 //   slot from the device pool, or falls back to the static walk if the pool cannot be created
 //   (first use inside a stream capture).
-}  // namespace rn_gemm_detail
-extern "C" int* rn_gemm_sched_slot(int dev, hipStream_t st);
-extern "C" int rn_gemm_get_reserve();
-namespace rn_gemm_detail {
 // non-temporal output stores: plain bf16 outputs over 1 GiB (a 256 MiB threshold also caught outputs
 // the next kernel reads at once, +0.14-0.4 ms per GPT-2-small step, profiles/r3s_resume_xent_gelu.txt
 // item 17)

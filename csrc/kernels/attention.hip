@@ -37,6 +37,7 @@
 // Round 6 (D = 64): the 32×32×16 forward (causal: 8 waves / 256 queries per workgroup), and for
 // Tq, Tk ≤ 256 whole-head-resident forward / backward kernels (docs/DESIGN.md §4 has the selection table).
 #include "attention_common.h"
+#include "rn_api.h"
 
 #include <algorithm>
 #include <map>
@@ -180,7 +181,6 @@ using namespace rn_attn;
 
 extern "C" {
 
-// strides in elements: [b, t, h] for q, k, v, o ; d is contiguous
 int rn_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const float* bias, int bias_b,
                 const long* strides, int B, int H, int Tq, int Tk, int D, float scale, int causal, float p_drop,
                 uint64_t seed, const uint64_t* seed_ptr, hipStream_t st) {
@@ -202,10 +202,6 @@ int rn_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse
     }
 }
 
-void rn_fp8_roll_bf8(float* state, hipStream_t st);  // fp8.hip
-long rn_attn_q8_part_floats(int B, int H, int Tq, int Tk);
-
-// strides: q,k,v,o,do,dq,dk,dv (each b,t,h).  delta: B*H*Tq floats workspace.
 int rn_attn_bwd(const void* dout, const void* q, const void* k, const void* v, const void* o, const float* lse,
                 const float* bias, int bias_b, void* dq, void* dk, void* dv, float* delta, const long* s, int B, int H,
                 int Tq, int Tk, int D, float scale, int causal, float p_drop, uint64_t seed, const uint64_t* seed_ptr,

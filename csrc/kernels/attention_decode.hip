@@ -18,6 +18,7 @@
 // gives a zero row.  Same indexing, same reduction order: with lens[b] == Tk it is the unmasked
 // kernel bit for bit.
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -109,9 +110,6 @@ __global__ void __launch_bounds__(DEC_T) attn_decode64_k(const bf16* __restrict_
 
 }  // namespace
 
-// q, o: (B, 1, H, 64); k, v: (B, Tk, H, 64) with the given element strides (unit D stride);
-// mask: Tk fp32 additive (or null); lens (with no mask): B per-row key counts, int64 if lens64 else
-// int32.  Returns -1 for shapes this kernel does not take.
 extern "C" int rn_attn_decode(const void* q, const void* k, const void* v, const float* mask, const void* lens,
                               int lens64, void* o, int B, int H, int Tk, int D, const long* s, float scale,
                               hipStream_t st) {

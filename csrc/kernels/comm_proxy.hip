@@ -9,6 +9,7 @@
 //     workgroups hold their CUs for as long as the real collective would.
 // Pacing uses the 100 MHz constant clock (s_memrealtime) with s_sleep between chunks.
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 

@@ -6,6 +6,7 @@
 // 16-byte channel chunk.  col2im is a gather (each input pixel sums the column
 // entries that read it): deterministic, no atomics.
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -602,7 +603,6 @@ void rn_col2im(const void* dcols, void* dx, int N, int H, int W, int C, int KH, 
                                                           Kp, accumulate);
 }
 
-// idx: one byte per output element (window position of the first maximum); K*K <= 256
 void rn_maxpool_fwd(const void* x, void* y, void* idx, int N, int H, int W, int C, int K, int S, int P, int OH,
                     int OW, hipStream_t st) {
     if (C % 8 == 0)
@@ -636,7 +636,6 @@ void rn_avgpool_bwd(const void* gy, void* dx, int N, int HW, int C, hipStream_t 
     avgpool_bwd_k<<<gridn((long)N * HW * C), 256, 0, st>>>((const bf16*)gy, (bf16*)dx, N, HW, C);
 }
 
-// workspace floats: partials [S][2C] + reduced sums [2C] + the column reduction's scratch
 long rn_bn_ws_floats(int M, int C) { return 2L * C * (bn_splits(M) + 1) + (long)RN_COLRED_S * 2 * C; }
 
 static void bn_stats(int mode, const void* a, const void* xin, const uint8_t* mk, const float* mean, const float* rstd,
@@ -658,9 +657,6 @@ static void bn_stats(int mode, const void* a, const void* xin, const uint8_t* mk
 
 int rn_bn_supported(int C) { return C % 8 == 0 && C <= 2048; }
 
-// res (optional): y = relu(BN(x) + res).  partials (optional): [prows][2C] Σx | Σx² row-block partials
-// from x's producer (the implicit-conv GEMM epilogue): only their fixed-order column reduction runs,
-// not a statistics pass over x.  mask (optional, with relu): [M·C/8] bytes of relu'(y) bits.
 void rn_bn_fwd(const void* x, const void* w, const void* b, float* rmean, float* rvar, void* y, float* mean,
                float* rstd, float* ws, int M, int C, float mom, float eps, int relu, const void* res,
                const float* partials, int prows, void* mask, hipStream_t st) {
@@ -686,9 +682,8 @@ void rn_bn_eval(const void* x, const void* w, const void* b, const float* rmean,
                                                  (const bf16*)res, (bf16*)y, nullptr, t8, C, eps, relu);
 }
 
-// dw/db: bf16 outputs [C] (the parameter dtype, written by the reduction itself; with `accum` ADDED
-// into them: the flat gradient buffer's views, no AccumulateGrad pass); gres (optional):
-// dy ⊙ relu'(y), the gradient of a fused residual input; mask: the forward's relu'(y) bits (relu only)
+// (dw/db: the parameter dtype, written by the reduction itself; with `accum` the flat gradient buffer's
+// views, no AccumulateGrad pass)
 void rn_bn_bwd(const void* gy, const void* x, const void* mask, const void* w, const float* mean, const float* rstd,
                void* dx, void* dw, void* db, float* ws, int M, int C, int relu, void* gres, int accum,
                hipStream_t st) {

@@ -27,6 +27,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -241,8 +242,6 @@ bool conv3x3_on() {
 
 extern "C" {
 
-// tiles (rows of the statistics partials) of the halo-tile conv for this shape; 0 = not taken (the implicit
-// GEMM runs instead)
 int rn_conv3x3_tiles(int N, int H, int W) {
     if (!conv3x3_on()) return 0;
     int fm = 0;
@@ -250,8 +249,6 @@ int rn_conv3x3_tiles(int N, int H, int W) {
     return tr == 0 ? 0 : N * (H / tr);
 }
 
-// in / out NHWC [N][H][W][64], w [64][3][3][64]; dgrad: out = dx from in = dy (w flipped / transposed);
-// part: forward statistics [tiles][128] (or null); accumulate: out += result.  Returns -1 if not taken.
 int rn_conv3x3(const void* in, const void* w, void* out, float* part, int N, int H, int W, int dgrad, int accumulate,
                hipStream_t st) {
     const int tiles = rn_conv3x3_tiles(N, H, W);

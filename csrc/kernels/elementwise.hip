@@ -2,6 +2,7 @@
 // add(+relu).  Memory-bound: every kernel moves bf16 as 16-byte vectors
 // (8 elements / lane), grid-strides over at most 256 CUs x 8 blocks.
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -194,7 +195,6 @@ void rn_add(const void* a, const void* b, void* y, long n, int relu, hipStream_t
     else add_k<false><<<g, TPB, 0, st>>>((const bf16*)a, (const bf16*)b, (bf16*)y, n);
 }
 
-// part: workspace of >= (splits + RN_COLRED_S) * N floats.  db (fp32) / db16 (bf16) written if want_bias.
 void rn_bias_act_grad(const void* dy, const void* h, void* dh, float* db, void* db16, float* part, int M, int N,
                       int act, int want_bias, int accum, hipStream_t st) {
     int cblocks = (N + 511) / 512;
@@ -210,7 +210,6 @@ void rn_bias_act_grad(const void* dy, const void* h, void* dh, float* db, void* 
     if (want_bias) rn_colreduce(part, splits, N, part + (long)splits * N, db, (bf16*)db16, st, accum);
 }
 
-// out16[c] (+)= Σ_r in[r][c] for an fp32 [R][C] partial matrix (tmp: RN_COLRED_S * C floats).
 void rn_colsum_f32(const float* in, int R, int C, float* tmp, void* out16, int accum, hipStream_t st) {
     rn_colreduce(in, R, C, tmp, nullptr, (bf16*)out16, st, accum);
 }

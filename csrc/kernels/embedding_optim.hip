@@ -1,5 +1,6 @@
 // Embedding gather / scatter-add (N14) and fused optimizer steps (N12/N13).
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -337,7 +338,6 @@ void rn_emb_fwd(const int64_t* ids, const void* wte, const void* wpe, void* x, i
     else emb_fwd_k<false><<<g, 256, 0, st>>>(ids, (const bf16*)wte, nullptr, (bf16*)x, rows, T, E, V);
 }
 
-// dwte32: V*E fp32 scratch (zeroed here); dwte: bf16 out; dwpe: bf16 (Tp*E) or null
 void rn_emb_bwd(const int64_t* ids, const void* dx, float* dwte32, void* dwte, void* dwpe, int B, int T, int Tp,
                 int V, int E, hipStream_t st) {
     int rows = B * T;
@@ -348,7 +348,6 @@ void rn_emb_bwd(const int64_t* ids, const void* dx, float* dwte32, void* dwte, v
     if (dwpe) emb_bwd_pos_k<<<rn_cdiv((long)Tp * E, 256), 256, 0, st>>>((const bf16*)dx, (bf16*)dwpe, B, T, Tp, E);
 }
 
-// E % 4 == 0.  gwte (bf16 V×E) and gwpe (bf16 ≥T×E, may be null) are accumulated into.
 void rn_emb_bwd_acc(const int64_t* ids, const void* dx, float* d32, unsigned* owner, void* gwte, void* gwpe, int B,
                     int T, int E, int V, hipStream_t st) {
     const int rows = B * T;
@@ -421,7 +420,6 @@ __global__ void __launch_bounds__(256) vit_join_bwd_k(const bf16* __restrict__ d
     }
 }
 
-// deterministic variant: d64 = persistent zeroed V×E 64-bit scratch
 void rn_emb_bwd_acc_det(const int64_t* ids, const void* dx, void* d64, unsigned* owner, void* gwte, void* gwpe, int B,
                         int T, int E, int V, hipStream_t st) {
     const int rows = B * T;
@@ -443,7 +441,6 @@ void rn_vit_join_bwd(const void* dx, void* dpatch, void* gcls, void* gpos, int B
 
 int rn_norm_ws_floats() { return NORM_BLOCKS; }
 
-// normbuf[0] = sum(g^2), normbuf[1] = 0 (skip flag); part: NORM_BLOCKS floats
 void rn_sumsq(const void* g, long n, int is_bf16, float* part, float* normbuf, hipStream_t st) {
     int gb = grid_for(n / 8);
     if (gb > NORM_BLOCKS) gb = NORM_BLOCKS;

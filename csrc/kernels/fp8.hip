@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "gemm_impl.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -349,15 +350,8 @@ int fp8_gemm_kernel() {
 
 }  // namespace
 
-void rn_gemm_launch_pk_fp8(rn_gemm_detail::GemmArgs& a, int act, hipStream_t st);
-int rn_gemm_launch_w1(rn_gemm_detail::GemmArgs& a, int fp8, int act, hipStream_t st, bool bmn);
-int rn_gemm_launch_w1_wgrad(rn_gemm_detail::GemmArgs& a, int fp8, int split, hipStream_t st);
-void rn_gemm_launch_pk_fp8_wgrad(rn_gemm_detail::GemmArgs& a, int a_bf8, hipStream_t st);
-void rn_gemm_launch_pk_fp8_dgrad(rn_gemm_detail::GemmArgs& a, int a_bf8, hipStream_t st);
-
 extern "C" {
 
-// state must hold >= 2 floats; it is (re)initialised here (memset node + 2 kernels).
 void rn_fp8_quantize(const void* x, long n, void* q, float* state, hipStream_t st) {
     // all 4 slot floats: a first (current-scaling) quantisation is copied whole into a training slot,
     // whose [2] / [3] must not carry uninitialised bytes (run-to-run bitwise state_dicts)
@@ -366,15 +360,14 @@ void rn_fp8_quantize(const void* x, long n, void* q, float* state, hipStream_t s
     quant_k<<<gridn(n / 8 + 1), 256, 0, st>>>((const bf16*)x, n, (uint8_t*)q, state);
 }
 
-// One-pass delayed-scaling quantisation (state as fp8_roll_k / quant_delayed_k); graph-capturable.
+// (state as fp8_roll_k / quant_delayed_k)
 void rn_fp8_quantize_delayed(const void* x, long n, void* q, float* state, hipStream_t st) {
     fp8_roll_k<<<1, 1, 0, st>>>(state, fp8_hr());
     quant_delayed_k<<<gridn(n / 8 + 1), 256, 0, st>>>((const bf16*)x, n, (uint8_t*)q, state);
 }
 
-// Re-quantise every cached fp8 weight (segs: device int64 [nseg][4], see fp8_quant_many_k).
-// roll = 0: keep the scales already in the slots (rebuilding the cache after a checkpoint load: the
-// bytes and the recorded amax are then exactly those of the saving run's last refresh).
+// (segs: see fp8_quant_many_k; with roll = 0 the bytes and the recorded amax are exactly those of the
+// saving run's last refresh)
 void rn_fp8_quant_many(const void* flat, const long* segs, int nseg, long max_n, void* qbuf, int roll,
                        hipStream_t st) {
     if (nseg <= 0) return;
@@ -384,15 +377,12 @@ void rn_fp8_quant_many(const void* flat, const long* segs, int nseg, long max_n,
     fp8_quant_many_k<<<dim3(bx, nseg), 256, 0, st>>>((const bf16*)flat, segs, (uint8_t*)qbuf);
 }
 
-// The delayed-scaling roll alone (for producers that quantise inside their own kernel).
 void rn_fp8_roll(float* state, hipStream_t st) { fp8_roll_k<<<1, 1, 0, st>>>(state, fp8_hr()); }
 
 void rn_fp8_dequantize(const void* q, long n, const float* state, void* y, hipStream_t st) {
     dequant_k<<<gridn(n), 256, 0, st>>>((const uint8_t*)q, n, state, (bf16*)y);
 }
 
-// e5m2 gradient quantisation: delayed (roll + one pass) or, for a slot without a scale yet,
-// current scaling (memset + amax + quantise); state as rn_fp8_quantize_delayed
 void rn_bf8_quantize(const void* x, long n, void* q, float* state, int delayed, hipStream_t st) {
     if (delayed) {
         fp8_roll_bf8_k<<<1, 1, 0, st>>>(state, fp8_ghr());
@@ -479,9 +469,7 @@ void rn_bf8_dequantize(const void* q, long n, const float* state, void* y, hipSt
     dequant_bf8_k<<<gridn(n), 256, 0, st>>>((const uint8_t*)q, n, state, (bf16*)y);
 }
 
-// C[M,N] (bf16) = act(sa·sb · A8[M,K] · B8[N,K]ᵀ + bias) + res ; K % 16 == 0, lda/ldb in bytes % 16 == 0
-// q8 / q8st (optional, activation-forward with a saved pre-activation only): also write the output
-// in e4m3 for the next fp8 GEMM (q8st rolled here; the tile kernel's epilogue quantises and records amax)
+// (q8: the tile kernel's epilogue quantises and records amax)
 int rn_gemm_fp8(const void* A8, const void* B8, void* C, const void* bias, const void* res, void* pre,
                 const float* sa, const float* sb, float* alpha_ws, int M, int N, int K, long lda, long ldb, long ldc,
                 int act, hipStream_t st, void* q8, float* q8st) {
@@ -525,11 +513,7 @@ int rn_gemm_fp8(const void* A8, const void* B8, void* C, const void* bias, const
     return 0;
 }
 
-// dW[M,N] (+)= sa·sb · Σ_k A8[k][m] · B8[k][n]  — the fp8 weight gradient with both operands as the
-// forward / backward produced them (token-major: A8 = dY [K][lda] e5m2 or e4m3, B8 = X [K][ldb]
-// e4m3; lda / ldb in bytes), K = tokens.  C: bf16 (out_f32 = 0) or fp32, accumulated into when
-// `accumulate`.  ws: split · M · N floats (rn_gemm_fp8_wgrad_ws).  Requirements: M, N, lda, ldb
-// multiples of 16, K a multiple of 128.
+// the fp8 weight gradient (contract: rn_api.h); its split-K slab count:
 long rn_gemm_fp8_wgrad_split(int M, int N, int K) {
     // K slices of whole 128-deep K-tiles, an exact division of the K-tiles (the one-wave-per-SIMD kernel's
     // split-K walk) with >= 2 per slice: the divisor with the shortest makespan over 256 CUs, each item
@@ -577,10 +561,7 @@ int rn_gemm_fp8_wgrad(const void* A8, const void* B8, void* C, const float* sa, 
     return 0;
 }
 
-// C[M,N] (bf16) = sa·sb · A8[M][K] · B8[K][N]: the fp8 data gradient dX = dY·W with dY (A8, e5m2 if
-// a_bf8) K-contiguous and the weight W [out = K][in = N] as stored (the forward's e4m3 weight copy),
-// read transposed.  K, N, lda, ldb, ldc multiples of 16 (bytes for the fp8 operands).
-// post (optional device scalar): one more output multiplier (the fp8 LM head's g / n)
+// (post: the fp8 LM head's g / n)
 int rn_gemm_fp8_dgrad(const void* A8, const void* B8, void* C, const float* sa, const float* sb, float* alpha_ws,
                       int M, int N, int K, long lda, long ldb, long ldc, int a_bf8, hipStream_t st, const float* post) {
     if (K % 16 || N % 16 || lda % 16 || ldb % 16 || ldc % 8 || M <= 0) return -1;

@@ -45,28 +45,12 @@
 #include <mutex>
 
 #include "common.h"
+#include "rn_api.h"
 
 #include "gemm_pk.h"
 
 using rn_gemm_detail::GemmArgs;
 using rn_gemm_detail::BK;
-
-void rn_gemm_launch_cfg0(GemmArgs&, bool, bool, int, hipStream_t);
-int rn_gemm_launch_w1(GemmArgs& a, int fp8, int act, hipStream_t st, bool bmn);  // gemm_w1.hip (cfg 11)
-void rn_gemm_launch_cfg1(GemmArgs&, bool, bool, int, hipStream_t);
-void rn_gemm_launch_cfg2(GemmArgs&, bool, bool, int, hipStream_t);
-void rn_gemm_launch_cfg3(GemmArgs&, bool, bool, int, hipStream_t);
-void rn_gemm_launch_cfg4(GemmArgs&, bool, bool, int, hipStream_t);
-void rn_gemm_launch_cfg5(GemmArgs&, bool, bool, int, hipStream_t);
-void rn_gemm_launch_cfg6(GemmArgs&, bool, bool, int, hipStream_t);
-void rn_gemm_launch_cfg8(GemmArgs&, bool, bool, int, hipStream_t);
-void rn_gemm_launch_pk_tt(GemmArgs&, int, hipStream_t);
-void rn_gemm_launch_pk_tf(GemmArgs&, int, hipStream_t);
-void rn_gemm_launch_pk_ff(GemmArgs&, int, hipStream_t);
-void rn_gemm_launch_pk_ft(GemmArgs&, int, hipStream_t);
-#ifdef REPLICANN_DEV
-int rn_gemm_launch_pk_dbg(GemmArgs&, bool, bool, int, hipStream_t);
-#endif
 
 namespace {
 
@@ -197,32 +181,21 @@ int* rn_gemm_sched_slot(int dev, hipStream_t st) {
     return s < 0 ? nullptr : g_pool[dev] + (size_t)s * rn_gemm_detail::PK_SCHED_INTS;
 }
 
-// Workspace floats needed for a split-K launch.
 long rn_gemm_ws_floats(int M, int N, int split) { return split > 1 ? (long)split * M * N : 0; }
 
-// C[M,N] = act(alpha · op(A)[M,K] · op(B)[K,N] + bias) + res.
-//   trans_a = 0: A stored [M][lda] (K contiguous);   1: A stored [K][lda] (M contiguous)
-//   trans_b = 0: B stored [K][ldb] (N contiguous);   1: B stored [N][ldb] (K contiguous)
-//   cfg: -1 auto, 0 = 128x128, 1 = 256x256 pipelined, 2 = 256x128 pipelined, 3 = 128x256,
-//        4 = 256x256 simple, 5 = 128x128 pipelined, 6 = 256x192 pipelined, 8 = 256x128 3-stage ring,
-//        9 = persistent 256x256 half-tile stream (gemm_pk.h; needs N % 8 == 0, ldc % 8 == 0)
-//        10 = skinny-M forward GEMM for decoding (gemm_skinny.hip; M <= 64, x·Wᵀ layout, split = K ranges),
-//        (7 is the vendor-library candidate handled in the bindings, off by default);
-//        split: -1 auto, 0/1 none
-// Returns 0, or -1 if the shape violates the kernel's alignment rules.
-// colpart (optional, act-backward only): [ceil(M / BM)][N] fp32 per-M-tile column sums of C
-// (BM of the config actually used: rn_gemm_cfg_bm).  Returns -3 if the requested config /
-// split cannot produce them (the caller then reduces C itself).
 int rn_gemm_cfg_bm(int cfg) { return (cfg == 0 || cfg == 3 || cfg == 5 || cfg == 9) ? 128 : 256; }
-// rows of the column-partial matrix a config writes (cfg 9: one row per (256-row tile, wave row))
+// (cfg 9: one row per (256-row tile, wave row))
 long rn_gemm_colpart_rows(int cfg, int M) {
     return (cfg == 9) ? 2L * ((M + 255) / 256) : (long)((M + rn_gemm_cfg_bm(cfg) - 1) / rn_gemm_cfg_bm(cfg));
 }
 
-int rn_gemm_skinny(const void* A, const void* W, void* C, const void* bias, const void* res, void* pre, float* ws,
-                   const float* alpha, int M, int N, int K, long lda, long ldw, long ldc, int trans_a, int trans_b,
-                   int act, int split, int out_f32, int accumulate, const float* colpart, hipStream_t st);
-
+// The contract is in rn_api.h.  Tile configs:
+//   cfg: -1 auto, 0 = 128x128, 1 = 256x256 pipelined, 2 = 256x128 pipelined, 3 = 128x256,
+//        4 = 256x256 simple, 5 = 128x128 pipelined, 6 = 256x192 pipelined, 8 = 256x128 3-stage ring,
+//        9 = persistent 256x256 half-tile stream (gemm_pk.h; needs N % 8 == 0, ldc % 8 == 0)
+//        10 = skinny-M forward GEMM for decoding (gemm_skinny.hip; M <= 64, x·Wᵀ layout, split = K ranges),
+//        11 = one-wave-per-SIMD persistent kernel (gemm_w1.h),
+//        (7 is the vendor-library candidate handled in the bindings, off by default)
 int rn_gemm(const void* A, const void* B, void* C, const void* bias, const void* res, void* pre, float* ws,
             const float* alpha, int M, int N, int K, long lda, long ldb, long ldc, int trans_a, int trans_b, int act,
             int split, int out_f32, int accumulate, int cfg, hipStream_t st, float* colpart) {

@@ -6,6 +6,7 @@
 //   mode 3  wgrad  dw[oc][k]     = Σ_pix dy[pix][oc] · x̂[pix][k]      (B gathered, split-K over pixels)
 // All on the NS = 3 stage ring of gemm_impl.h.
 #include "gemm_impl.h"
+#include "rn_api.h"
 
 using namespace rn_gemm_detail;
 
@@ -48,7 +49,6 @@ void rn_conv_wgrad_tile(int M, int N, int* bm, int* bn) {
     *bn = BNS[v];
 }
 
-// Returns 0, or -1 if the geometry is outside the implicit path (caller falls back to im2col).
 int rn_conv_gemm(int mode, const void* A, const void* B, void* C, const void* bias, float* ws, int M, int N, int K,
                  long lda, long ldb, long ldc, int H, int W, int Cg, int RH, int RW, int KH, int KW, int S, int P,
                  int KC, int BC, long bld, int split, int out_f32, int accumulate, float* colpart,

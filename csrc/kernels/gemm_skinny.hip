@@ -17,6 +17,7 @@
 // Epilogue order as the tile kernels': ·alpha, +bias, activation (with the optional
 // pre-activation / gelu' store of the bf16-rounded h), +residual.
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -158,9 +159,6 @@ void sk_launch(const SkArgs& a, int mb, hipStream_t st) {
 
 }  // namespace
 
-// Returns -1 for what this config does not take (the caller's autotuner then skips it): a
-// transposed operand, M > 64, accumulate, activation backward, column partials, split without a
-// workspace.  ``split``: K ranges (>= 1); each is a multiple of 32 deep.
 extern "C" int rn_gemm_skinny(const void* A, const void* W, void* C, const void* bias, const void* res, void* pre, float* ws,
                    const float* alpha, int M, int N, int K, long lda, long ldw, long ldc, int trans_a, int trans_b,
                    int act, int split, int out_f32, int accumulate, const float* colpart, hipStream_t st) {
@@ -187,10 +185,6 @@ extern "C" int rn_gemm_skinny(const void* A, const void* W, void* C, const void*
     return 0;
 }
 
-// Decode step QKV projection with the K|V append fused: out = x·Wᵀ + bias (M <= 64 rows = batch
-// rows, one new token each) and its columns >= kv_c0 (keys, values) also written into the KV cache
-// at the device-side row kv_pos[0] (kv_per_row 0) or kv_pos[m] of batch row m (kv_per_row 1), in a
-// cache of kv_len rows — the separate index_copy of every layer's keys / values is gone.
 extern "C" int rn_gemm_skinny_kv(const void* x, const void* W, const void* bias, void* C, int M, int N, int K,
                                  long ldx, long ldw, long ldc, void* kvd, const int64_t* kv_pos, int kv_per_row,
                                  int kv_len, long kv_sb, long kv_row, int kv_c0, hipStream_t st) {

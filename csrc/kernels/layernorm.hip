@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -301,7 +302,6 @@ extern "C" {
 
 int rn_ln_nv(int E) { return (E / 8 + 63) / 64; }
 
-// q8 / st8 (optional): fused e4m3 output with delayed scaling (st8 already rolled by the caller)
 int rn_ln_fwd(const void* x, const void* r, const void* w, const void* b, void* y, void* h, float* mean,
               float* rstd, int M, int E, float eps, hipStream_t st, void* q8, float* st8) {
     if (E % 8 != 0 || E > 8192) return -1;
@@ -340,14 +340,9 @@ int rn_ln_bwd_blocks(int M) {
 }
 int rn_ln_bwd_waves(int M) { return 4 * rn_ln_bwd_blocks(M); }
 
-// workspace floats: partial rows [blocks][3E] + the reduction's [RN_COLRED_S][3E] scratch
 long rn_ln_bwd_ws(int M, int E) { return 3L * (rn_ln_bwd_blocks(M) + RN_COLRED_S) * E; }
 
-// ws: rn_ln_bwd_ws(M, E) floats.  dw/db (fp32) and dw16/db16 (bf16) outputs, any may be null.
-// dxs16 (optional, bf16, always accumulated into): Σ_rows dx — the bias gradient of the layer
-// that produced this LayerNorm's input.
-void rn_fp8_roll_bf8(float* state, hipStream_t st);  // fp8.hip
-// q8 / q8st (optional): dx also in e5m2 with the consumer's delayed scale (q8st rolled here), see ln_bwd_k
+// (q8: see ln_bwd_k)
 int rn_ln_bwd(const void* dy, const void* gh, const void* h, const void* w, const float* mean, const float* rstd,
               void* dx, float* dw, float* db, void* dw16, void* db16, void* dxs16, float* ws, int M, int E,
               int accum, hipStream_t st, void* q8, float* q8st) {

@@ -29,6 +29,7 @@
 // Rows longer than the register budget (V + 7 > 57344) re-read the row from global memory in every
 // pass (R = 0): that path only has to be correct.
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -371,9 +372,6 @@ int launch(const void* logits, long ld, int B, int V, float temperature, int top
 
 }  // namespace
 
-// logits (B, V) bf16 / fp32 with row stride ld >= V; exactly one of u (B fp32 in [0, 1)) and seed
-// (row b draws hash_uniform(*seed, b)); params: 3 fp32 on the device (temperature, top_k, top_p)
-// overriding the host values, or null.  tokens (B) int64, kept (B) int32.
 extern "C" int rn_sample_logits(const void* logits, int is_bf16, long ld, int B, int V, float temperature, int top_k,
                                 float top_p, const float* params, const float* u, const uint64_t* seed,
                                 int64_t* tokens, int* kept, hipStream_t st) {

@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "rn_api.h"
 
 namespace {
 
@@ -373,8 +374,7 @@ void rn_xent_fwd(void* logits, const int64_t* tgt, float* loss, float* lse, int 
     if (write_grad) xent_fwd_k<true><<<M, TPB, 0, st>>>((bf16*)logits, tgt, loss, lse, V, nvalid, ignore);
     else xent_fwd_k<false><<<M, TPB, 0, st>>>((bf16*)logits, tgt, loss, lse, V, nvalid, ignore);
 }
-// the fp8 LM head's loss: rn_xent_fwd with write_grad, the gradient to q8 as e5m2 · 2^15 (xent_row2_k<.., true>);
-// -1 if V is outside the row kernel's range (the caller keeps the bf16 path)
+// (xent_row2_k<.., true>)
 int rn_xent_fwd_q8(void* logits, const int64_t* tgt, float* loss, float* lse, int M, int V, int nvalid, long ignore,
                    void* q8, hipStream_t st) {
     if (V % 8 || V > 8 * 1024 * 8) return -1;
