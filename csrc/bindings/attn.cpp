@@ -1,5 +1,6 @@
-// Attention and decoding bindings: attn_fwd and the backward forms, attn_decode, linear_kv, sample_logits
-// (kernels: attention*.hip, attention_decode.hip, gemm_skinny.hip, sampling.hip).  Not named attention.cpp:
+// Attention and decoding bindings: attn_fwd and the backward forms, attn_decode, attn_window, linear_kv,
+// sample_logits (kernels: attention*.hip, attention_decode.hip, attention_window.hip, gemm_skinny.hip,
+// sampling.hip).  Not named attention.cpp:
 // the build keys its per-unit compiler flags by file stem, and those of attention.hip are for device code.
 #include "binding_util.h"
 #include "rn_api.h"
@@ -77,6 +78,49 @@ Tensor attn_decode(const Tensor& q, const Tensor& k, const Tensor& v, const opti
                                   has_lens && lens->scalar_type() == at::kLong ? 1 : 0, o.data_ptr(), B, H, Tk, D,
                                   s.data(), (float)scale, cur_stream());
     TORCH_CHECK(rc == 0, "attn_decode: unsupported shape D=", D, " Tk=", Tk, " (D == 64, Tk <= 1024)");
+    return o;
+}
+
+// window attention with the cache append folded in (attention_window.hip): qkv (B, T, 3, H, 64), possibly a
+// strided view of the projection output; kv (B, L, 2, H, 64) the layer's cache buffer; pos (B,) int32 / int64
+// first write rows (clamped to [0, L] on the device) -> o (B, T, H, 64).  Query i of row b attends cache
+// rows < pos[b] and window rows <= i; window rows that fit are written to kv[b, pos[b] + i].
+Tensor attn_window(const Tensor& qkv, Tensor& kv, const Tensor& pos, double scale) {
+    CHECK_CUDA(qkv); CHECK_BF16(qkv); CHECK_BF16(kv); GUARD(qkv);
+    TORCH_CHECK(qkv.dim() == 5 && qkv.size(2) == 3, "attn_window: qkv must be (B, T, 3, H, D), got ", qkv.sizes());
+    const int64_t B = qkv.size(0), T = qkv.size(1), H = qkv.size(3), D = qkv.size(4);
+    TORCH_CHECK(kv.dim() == 5 && kv.size(0) == B && kv.size(2) == 2 && kv.size(3) == H && kv.size(4) == D,
+                "attn_window: kv must be (B, L, 2, H, D) for qkv ", qkv.sizes(), ", got ", kv.sizes());
+    const int64_t L = kv.size(1);
+    TORCH_CHECK(T >= 1 && T <= 16, "attn_window: T = ", T, " outside 1..16");
+    TORCH_CHECK(D == 64, "attn_window: head size ", D, " (64 only)");
+    TORCH_CHECK(L >= 1 && L <= 1024, "attn_window: cache length ", L, " outside 1..1024");
+    TORCH_CHECK(H >= 1 && B * H <= (int64_t)1 << 30, "attn_window: B * H out of range");
+    TORCH_CHECK(pos.dim() == 1 && pos.size(0) == B && pos.is_contiguous(),
+                "attn_window: pos must be a contiguous (B,) tensor, got ", pos.sizes());
+    TORCH_CHECK(pos.scalar_type() == at::kInt || pos.scalar_type() == at::kLong,
+                "attn_window: pos must be int32 or int64, got ", pos.scalar_type());
+    TORCH_CHECK(kv.device() == qkv.device() && pos.device() == qkv.device(),
+                "attn_window: qkv, kv and pos must be on one device");
+    // the kernel moves 16-B vectors: base pointers and every non-unit stride 16-B aligned
+    std::vector<long> qs, cs;
+    for (int d : {0, 1, 2, 3}) { qs.push_back(qkv.stride(d)); cs.push_back(kv.stride(d)); }
+    for (const Tensor* t : {&qkv, static_cast<const Tensor*>(&kv)}) {
+        TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0 && t->stride(4) == 1,
+                    "attn_window: qkv / kv need a 16-byte aligned base and a contiguous head dimension");
+        for (int d = 0; d < 4; ++d)
+            TORCH_CHECK(t->stride(d) % 8 == 0 && t->stride(d) >= 0, "attn_window: qkv / kv strides must be multiples of 8 elements");
+    }
+    // the append writes through kv's strides: its rows must not overlap
+    TORCH_CHECK(kv.stride(3) >= D && kv.stride(2) >= H * kv.stride(3) && kv.stride(1) >= 2 * kv.stride(2) &&
+                    (B == 1 || kv.stride(0) >= L * kv.stride(1)),
+                "attn_window: kv must be a dense (B, L, 2, H, D) layout, got strides ", kv.strides());
+    Tensor o = at::empty({B, T, H, D}, qkv.options());
+    if (B == 0) return o;
+    const int rc = rn_attn_window(qkv.data_ptr(), kv.data_ptr(), pos.data_ptr(), pos.scalar_type() == at::kLong ? 1 : 0,
+                                  o.data_ptr(), (int)B, (int)T, (int)H, (int)L, (int)D, qs.data(), cs.data(),
+                                  (float)scale, cur_stream());
+    TORCH_CHECK(rc == 0, "attn_window: unsupported shape T=", T, " D=", D, " L=", L);
     return o;
 }
 
@@ -236,6 +280,15 @@ TORCH_LIBRARY_FRAGMENT(replicann, m) {
     m.def("attn_bwd_out_q8(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor? bias, float scale, "
           "bool causal, float p, int seed, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, "
           "Tensor(d!)? qkv_bias_grad, Tensor? seed_buf, Tensor(e!) q8, Tensor(f!) q8_state, bool q8_only) -> bool");
+}
+
+// decoding ops added after the replicann:: list was frozen live in a namespace of their own
+TORCH_LIBRARY_FRAGMENT(replicann_decode, m) {
+    m.def("attn_window(Tensor qkv, Tensor(a!) kv, Tensor pos, float scale) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(replicann_decode, CUDA, m) {
+    m.impl("attn_window", &attn_window);
 }
 
 TORCH_LIBRARY_IMPL(replicann, CUDA, m) {

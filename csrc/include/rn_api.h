@@ -215,6 +215,14 @@ int rn_attn_decode(const void* q, const void* k, const void* v, const float* mas
                    int lens64, void* o, int B, int H, int Tk, int D, const long* s, float scale,
                    hipStream_t st);
 
+// ------------------------------------------------------------------ attention_window.hip
+// T (1..16) new tokens per batch row against a KV cache, append included: qkv (B, T, 3, H, 64) with the
+// element strides qs (batch, token, q|k|v, head), kv (B, L <= 1024, 2, H, 64) with cs (batch, row, k|v,
+// head), pos: B first write rows (int64 if pos64 else int32, clamped to [0, L] on the device), o
+// (B, T, H, 64) contiguous.  Returns -1 for shapes or strides this kernel does not take.
+int rn_attn_window(const void* qkv, void* kv, const void* pos, int pos64, void* o, int B, int T, int H,
+                   int L, int D, const long* qs, const long* cs, float scale, hipStream_t st);
+
 // ------------------------------------------------------------------ sampling.hip
 // logits (B, V) bf16 / fp32 with row stride ld >= V; exactly one of u (B fp32 in [0, 1)) and seed
 // (row b draws hash_uniform(*seed, b)); params: 3 fp32 on the device (temperature, top_k, top_p)

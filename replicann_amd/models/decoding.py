@@ -3,10 +3,13 @@
 ``KVCache`` owns everything that depends on its mode; ``generate`` is the sampling loop (uniform or
 ragged) over one ``_StepDriver``, which resolves the cache and runs the one-token step eagerly or as
 a hipGraph kept in the model's ``_GraphRegistry``.  The model (``models/gpt2.py``) keeps the pass.
+With a draft model, ``generate`` is greedy speculative decoding (``_speculative_loop``): the draft's
+one-token steps, the target's window step (``_WindowDriver``, ``capture_window``) and ``accept``.
 """
 
 from __future__ import annotations
 
+import contextlib
 import os
 import weakref
 
@@ -31,6 +34,8 @@ class KVCache:
         row, ``lens = pos_t + 1`` the key count its attention reads once this step's row is appended
         (no mask: rows past it are never read), ``active`` (B,) 0 / 1 the rows that advance (0: a
         finished row stays where it is).  ``pos`` is max over the rows: an upper bound.
+        Only this mode has the window step (``windowed`` / ``window`` / ``advance`` / ``set_rows``): T
+        tokens per row written and attended at each row's own position, committed separately.
     A captured step reads the device tensors by address, so each is allocated once per cache and kept
     through ``reset()`` and every mode change (the per-sequence triple: until the batch size changes)."""
 
@@ -39,6 +44,18 @@ class KVCache:
         self.kv = [None] * n_layer
         self._pos1 = self.mask = None  # device mode
         self._rows = self.lens = self.active = None  # per-sequence mode
+        self.in_window = False  # inside ``windowed()``: the pass is the window step
+
+    @contextlib.contextmanager
+    def windowed(self):
+        """The pass inside is the window step (``GPT2.decode_window``): ``embed`` reads T position rows
+        per batch row and the attention layers call ``window`` instead of ``update`` / ``attend``."""
+        self._need_per_seq("windowed")
+        self.in_window = True
+        try:
+            yield self
+        finally:
+            self.in_window = False
 
     device_pos = property(lambda self: self.mode != "host")
     per_seq = property(lambda self: self.mode == "per_seq")
@@ -110,8 +127,45 @@ class KVCache:
             self.lens.add_(self.active)
         self.pos += T
 
+    # ---- the window step (per-sequence mode): T tokens per row, each row at its own position ----
+    def _need_per_seq(self, what):
+        if self.mode != "per_seq":
+            raise ValueError(f"KVCache.{what} needs a cache in per-sequence mode (a ragged prefill)")
+
+    def window(self, layer, qkv):
+        """Append the key / value rows of ``qkv`` (B, T, 3, H, D) at each row's position and attend its T
+        queries to the cached rows and the window so far: one ``ops.attention_window``.  The position
+        does not move (``advance``): whatever the window wrote past it stays unread."""
+        self._need_per_seq("window")
+        return ops.attention_window(qkv, self.kv[layer], self._rows)
+
+    def advance(self, counts, bound=None):
+        """Commit ``counts`` (B,) device integers of the rows a window step wrote: every active row moves
+        by its own count.  No host value is read; ``bound`` (a host integer, if given) becomes ``pos``,
+        the upper bound of the positions that eager steps check against max_len."""
+        self._need_per_seq("advance")
+        step = counts.to(self._rows.dtype) * self.active
+        self._rows.add_(step)
+        self.lens.add_(step)
+        if bound is not None:
+            self.pos = int(bound)
+
+    def set_rows(self, rows, bound=None):
+        """Put every row at position ``rows`` (B,) device integers — a draft cache following its target;
+        rows at or past the new position are stale from then on.  ``bound``: as in ``advance``."""
+        self._need_per_seq("set_rows")
+        self._rows.copy_(rows)
+        torch.add(self._rows, 1, out=self.lens)
+        if bound is not None:
+            self.pos = int(bound)
+
     def embed(self, idx, wte, wpe):
         """Token + position embedding of ``idx`` (B, T) at the cache position(s)."""
+        if self.in_window:  # row b's tokens at wpe[pos_t[b] + i], the index clamped to the table
+            self._need_per_seq("embed (window)")
+            B, T = idx.shape
+            at = (self._rows.view(B, 1) + torch.arange(T, device=idx.device)).clamp_(0, wpe.shape[0] - 1)
+            return ops.embedding(idx.reshape(1, -1), wte, wpe.index_select(0, at.view(-1))).view(B, T, -1)
         if self.mode == "host":
             return ops.embedding(idx, wte, wpe[self.pos: self.pos + idx.shape[1]])
         rows = wpe.index_select(0, self.pos_t)
@@ -190,19 +244,20 @@ DECODE_EOS_CHECK = 8  # ragged generate: "has every row finished?" is asked of t
 class _GraphRegistry(dict):
     """One model's captured decode steps kept across ``generate`` calls, least recently used first:
     (batch, cache length, dtype, device, parameter storage[, "ragged" for the per-sequence step]
-    [, "sampler" for a step captured together with the native sampler]) → (cache, graph, token buffer,
-    logits), so a serving loop captures once per (batch, length bucket).  A sampler entry holds the
+    [, "sampler" for a step captured together with the native sampler][, "window", T for the window step of
+    T tokens per row: its output is the greedy ids (B, T)]) → (cache, graph, token buffer, logits), so a serving loop captures once per (batch, length bucket).  A sampler entry holds the
     sampled tokens (B, 1) in place of the logits, then the device tensor its settings are read from:
     one graph whatever the temperature / top_k / top_p.
     At most DECODE_GRAPHS_MAX (REPLICANN_DECODE_GRAPHS, default 4) are kept; each holds its KV cache."""
 
-    def lookup(self, model, B, L, ragged, use, sampler=False):
+    def lookup(self, model, B, L, ragged, use, sampler=False, window=None):
         """(key, its stored entry — now the most recently used — or None).  The parameters' storage
         is part of the key: a graph reads them by address, so entries captured before a parameter was
         re-assigned (p.data = ...) are dropped here, whether or not this call will ``use`` a graph."""
         sig = tuple(p.data_ptr() for p in model.parameters())
         key = (B, L, model.wte.dtype, model.wte.device, sig) + (("ragged",) if ragged else ())
         key += ("sampler",) if sampler else ()
+        key += ("window", window) if window else ()  # the captured window step of this many tokens per row
         for k in [k for k in self if k[4] != sig]:
             del self[k]
         entry = self.pop(key, None) if use else None
@@ -270,6 +325,161 @@ def capture_step(model, cache, B, sampler=None):
     return (graph, tok, out) if sampler is None else (graph, tok, out, params)
 
 
+def capture_window(model, cache, B, T):
+    """Record the window step ``model.decode_window`` of ``T`` tokens per row as a hipGraph, the way
+    ``capture_step`` does (one eager warm-up on a side stream; ``cache`` — in per-sequence mode — is
+    put back after both runs, so the positions after the capture equal the positions before it; the
+    rows the runs wrote are past them: not valid).  Returns (graph, tok (B, T), ids (B, T)): the caller
+    writes the window's tokens into ``tok``, replays and reads the greedy ids."""
+    dev = model.wte.device
+    tok = torch.zeros(B, T, dtype=torch.long, device=dev)
+    snap = cache.snapshot()
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        model.decode_window(tok, cache)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    cache.restore(snap)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = model.decode_window(tok, cache)
+    cache.restore(snap)
+    return graph, tok, out
+
+
+def accept(drafts, greedy, *, budget=None, finished=None, eos=None, pad=0):
+    """What one round of greedy speculative decoding commits — a pure tensor function, no host value.
+
+    ``drafts`` (B, K): the draft model's tokens d_1 .. d_K after the pending token; ``greedy``
+    (B, K+1): the target's greedy token after each window position [pending, d_1 .. d_K].  With ``a``
+    the length of the prefix on which they agree (d_j == greedy[j-1] for j <= a), a row commits
+    d_1 .. d_a and the target's own token greedy[a]: the a + 1 tokens greedy[:a+1].  They are cut after
+    the first ``eos`` (kept) and at the row's ``budget`` (B,), the tokens it may still emit; a
+    ``finished`` (B,) row commits nothing.
+
+    Returns (count (B,), tokens (B, K+1), matched (B,)): how many tokens each row commits, the tokens
+    themselves (``pad`` past count) and the agreed length a before any cut."""
+    B, K = drafts.shape
+    j = torch.arange(K + 1, device=drafts.device).view(1, K + 1)
+    matched = (drafts == greedy[:, :K]).long().cumprod(1).sum(1)
+    count = matched + 1
+    if eos is not None:  # the first EOS among the committed tokens ends them
+        first = torch.where(greedy == eos, j, K + 1).amin(1)
+        count = torch.minimum(count, first + 1)
+    if budget is not None:
+        count = torch.minimum(count, budget.clamp(min=0))
+    if finished is not None:
+        count = count.masked_fill(finished, 0)
+    return count, torch.where(j < count.view(B, 1), greedy, torch.full_like(greedy, pad)), matched
+
+
+def _check_draft(model, draft, draft_k, temperature, need):
+    if temperature != 0:
+        raise ValueError("generate(draft=...) is greedy: temperature must be 0 (sampling with a draft model needs "
+                         "rejection sampling and is not supported)")
+    if not isinstance(draft_k, int) or not 1 <= draft_k <= 15:
+        raise ValueError(f"draft_k must be in 1..15, got {draft_k}")
+    for what, a, b in (("vocab_size", model.config.vocab_size, draft.config.vocab_size),
+                       ("device", model.wte.device, draft.wte.device), ("dtype", model.wte.dtype, draft.wte.dtype)):
+        if a != b:
+            raise ValueError(f"the draft model's {what} ({b}) differs from the target's ({a})")
+    for name, m in (("target", model), ("draft", draft)):
+        # the window writes draft_k rows past the last committed one, and wpe has no rows beyond block_size
+        if need + draft_k > m.config.block_size:
+            raise ValueError(f"prompt + new tokens + draft_k = {need + draft_k} exceeds the {name} model's block_size "
+                             f"{m.config.block_size}")
+
+
+class _WindowDriver:
+    """One speculative ``generate`` call's target side: the cache and the window step of T tokens per
+    row, eager or as a hipGraph kept in the model's registry under (..., "ragged", "window", T)."""
+
+    def __init__(self, model, B, length, T, graph):
+        length = min(model.config.block_size, -(-length // DECODE_LEN_BUCKET) * DECODE_LEN_BUCKET)
+        self.model, self.B, self.T, self.graph, self.graphs = model, B, T, graph, registry(model)
+        self.key, self.entry = self.graphs.lookup(model, B, length, True, graph, window=T)
+        self.cache = KVCache(model.config.n_layer, length) if self.entry is None else self.entry[0]
+        self.cache.reset()
+
+    def step(self, toks):
+        """Greedy ids (B, T) after every position of the window ``toks`` (B, T); a replay returns its static buffer."""
+        if not self.graph:
+            return self.model.decode_window(toks, self.cache)
+        if self.entry is None:
+            self.graphs.make_room()  # before the capture allocates
+            self.entry = self.graphs[self.key] = (self.cache, *capture_window(self.model, self.cache, self.B, self.T))
+        _, graph, buf, out = self.entry
+        buf.copy_(toks)
+        graph.replay()
+        return out
+
+
+def _speculative_loop(model, draft, idx, plens, max_new_tokens, K, eos, pad, use_graph, ragged, stats):
+    """Greedy generation of ``model`` with ``draft`` proposing K tokens a round (see ``generate``)."""
+    (B, Tm), dev = idx.shape, idx.device  # idx: the prompts cut to the longest one
+    if pad is None:
+        pad = eos if eos is not None else 0
+    need = Tm + max_new_tokens + K
+    target = _WindowDriver(model, B, need, K + 1, use_graph)
+    drafter = _StepDriver(draft, B, need, True, use_graph, (0, None, None, None), False)
+    lens = torch.tensor(plens, dtype=torch.long, device=dev)  # each row's length so far
+    # rows prompt ‖ generated, pad elsewhere (K + 1 spare columns: a round's padded tail lands in range)
+    tokens = torch.full((B, need + 1), pad, dtype=torch.long, device=dev)
+    keep = torch.arange(Tm, device=dev).unsqueeze(0) < lens.unsqueeze(1)
+    tokens[:, :Tm] = torch.where(keep, idx, tokens[:, :Tm])
+    j = torch.arange(K + 1, device=dev).view(1, K + 1)
+    # both models prefill the prompts; the target's first token is committed at once and is "pending": the
+    # last committed token, not yet in either cache (it goes to row cache.pos_t of both)
+    pending = model.decode_step(idx, target.cache, lens=plens).argmax(-1)
+    draft.decode_step(idx, drafter.cache, lens=plens)
+    tokens.scatter_(1, lens.view(B, 1), pending.view(B, 1))
+    lens += 1
+    budget = torch.full((B,), max_new_tokens - 1, dtype=torch.long, device=dev)
+    finished = budget <= 0
+    if eos is not None:
+        finished |= pending == eos
+    drafted, accepted = torch.zeros_like(lens), torch.zeros_like(lens)
+    rounds_run = torch.zeros((), dtype=torch.long, device=dev)
+    drafts = torch.empty(B, K, dtype=torch.long, device=dev)
+    # an unfinished row commits 1 .. K + 1 tokens a round: no row can be done before `least` rounds without an
+    # EOS, and every row is after `most`; in between the device is asked every DECODE_EOS_CHECK rounds
+    most, least = max_new_tokens - 1, -(-(max_new_tokens - 1) // (K + 1))
+    for r in range(most):
+        ask = (r % DECODE_EOS_CHECK == 0) if eos is not None else (r >= least and (r - least) % DECODE_EOS_CHECK == 0)
+        if r and ask and bool(finished.all()):
+            break  # the one host sync of the stop logic
+        # the host bound of every row's position in this round: pending's row, then up to K drafted rows
+        top = min(Tm + r * (K + 1), Tm + max_new_tokens - 1)
+        live = ~finished
+        drafter.cache.active.copy_(live)  # finished rows stay where they are
+        drafter.cache.pos = top
+        tok = pending.view(B, 1)
+        # K + 1 draft steps: the last one only writes d_K's cache row (needed when every draft is accepted)
+        for i in range(K + 1):
+            tok = drafter.step(tok).argmax(-1, keepdim=True)
+            if i < K:
+                drafts[:, i] = tok[:, 0]
+        greedy = target.step(torch.cat([pending.view(B, 1), drafts], 1))
+        count, out, matched = accept(drafts, greedy, budget=budget, finished=finished, eos=eos, pad=pad)
+        tokens.scatter_(1, lens.view(B, 1) + j, out)  # pad past count: those columns are not committed yet
+        pending = torch.where(count > 0, out.gather(1, (count - 1).clamp(min=0).view(B, 1))[:, 0], pending)
+        lens += count
+        budget -= count
+        drafted += K * live
+        accepted += matched * live
+        rounds_run += live.any()
+        finished = finished | (budget <= 0)
+        if eos is not None:
+            finished |= ((out == eos) & (j < count.view(B, 1))).any(1)
+        target.cache.advance(count, bound=min(top + K + 1, Tm + max_new_tokens))
+        drafter.cache.set_rows(target.cache.pos_t)
+    if stats is not None:
+        stats.update(rounds=int(rounds_run), drafted=drafted.clone(), accepted=accepted.clone())
+    if ragged:
+        return tokens[:, : int(lens.max())], lens
+    return tokens[:, : Tm + max_new_tokens]
+
+
 class _StepDriver:
     """One ``generate`` call's cache and one-token step.  With ``graph``, an earlier call's cache and
     captured step of the same key are reused; failing that the first ``step`` captures (and stores) one."""
@@ -325,7 +535,8 @@ class _StepDriver:
 
 @torch.no_grad()
 def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=None, generator=None, graph=None,
-             prompt_lens=None, eos_token_id=None, pad_token_id=None, sampler="torch"):
+             prompt_lens=None, eos_token_id=None, pad_token_id=None, sampler="torch", draft=None, draft_k=4,
+             stats=None):
     """Autoregressive sampling with a KV cache: ``idx`` (B, T0) prompt → (B, T0 + max_new_tokens).
     ``temperature`` 0 = greedy; ``top_k`` / ``top_p`` restrict sampling.  One prefill pass over the prompt, then one-token steps whose
     attention reads the cached keys / values (no recomputation of the prefix).  ``graph``
@@ -345,7 +556,19 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     output); from then on it emits ``pad_token_id`` (default: the EOS id, else 0) and its position
     stops.  Generation ends early once every row is finished (asked of the device every
     DECODE_EOS_CHECK steps).  Returns ``(tokens, lens)``: tokens (B, max(lens)), rows
-    ``prompt_b ‖ generated_b`` right-padded with the pad id, and lens (B,) each row's total length."""
+    ``prompt_b ‖ generated_b`` right-padded with the pad id, and lens (B,) each row's total length.
+
+    Speculative decoding (``draft``: a smaller model of the same vocabulary, device and dtype; greedy only,
+    ``temperature=0``): the output is this model's greedy generation, token for token up to near-ties of
+    the arithmetic, produced in rounds.  Both models prefill the prompts; a round replays the draft's
+    one-token step ``draft_k`` + 1 times from the last committed token (the extra step writes the last
+    draft's cache row; its output is dropped), runs this model's window step over the committed token
+    and the ``draft_k`` drafts (``decode_window``: one pass of about one step's cost), commits what
+    ``accept`` keeps — the agreed drafts plus one token of this model's own, cut at an EOS and at
+    ``max_new_tokens`` — and moves both caches to the committed position, all on the device.  The
+    return types are the same; ``stats`` (a dict) receives ``rounds`` and, per row, ``drafted`` and
+    ``accepted`` (draft tokens proposed / agreed with).  The caches hold ``draft_k`` rows more than the
+    tokens: prompt + ``max_new_tokens`` + ``draft_k`` must fit both models' block_size."""
     B, T0 = idx.shape
     ragged = prompt_lens is not None or eos_token_id is not None
     if top_p is not None and not 0.0 < top_p <= 1.0:
@@ -365,6 +588,19 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     if Tm + max_new_tokens > model.config.block_size:
         raise ValueError(f"prompt {Tm} + {max_new_tokens} new tokens exceeds block_size {model.config.block_size}")
     use_graph = (model.wte.is_cuda if graph is None else graph) and max_new_tokens > 2
+    if draft is not None:
+        if max_new_tokens < 1:
+            raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
+        _check_draft(model, draft, draft_k, temperature, Tm + max_new_tokens)
+        modes = [(m, m.training) for m in (model, draft)]
+        try:
+            for m, _ in modes:
+                m.eval()
+            return _speculative_loop(model, draft, idx[:, :Tm], plens, max_new_tokens, draft_k, eos_token_id,
+                                     pad_token_id, use_graph, ragged, stats)
+        finally:
+            for m, was in modes:
+                m.train(was)
     was_training = model.training
     model.eval()
     try:

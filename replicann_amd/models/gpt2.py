@@ -191,6 +191,28 @@ class GPT2(nn.Module):
         cache.end_step(T)
         return logits
 
+    def _window_logits(self, idx, cache):
+        """Logits (B, T, vocab) of the window ``idx`` (B, T) written at each row's own cache position
+        (per-sequence mode): the cached pass with the window attention, then the LM head on all B·T rows."""
+        with cache.windowed():
+            x = cache.embed(idx, self.wte, self.wpe)
+            prev = None
+            for i, blk in enumerate(self.h):
+                x = blk(x, prev, cache=cache, layer=i)
+                prev = blk.out_bias()
+            h = self.ln_f(x, producer_bias=prev)
+        return ops.linear(h, self.wte)[..., : self.config.vocab_size]
+
+    @torch.no_grad()
+    def decode_window(self, idx, cache):
+        """Greedy token ids (B, T) after every position of the window ``idx`` (B, T): position i of row
+        b is the model's next token given the row's cached prefix and ``idx[b, :i+1]``.  The window's
+        keys / values are written at rows pos_t[b] .. pos_t[b] + T - 1 but the cache position does not
+        move: the caller commits what it keeps with ``cache.advance(counts)``, and the rest is stale
+        rows that the next step overwrites.  No host value is used: capturable as a hipGraph
+        (``decoding.capture_window``)."""
+        return self._window_logits(idx, cache).argmax(-1)
+
     def _device_position_step(self, tok, cache):
         """The one-token step ``tok`` (B, 1) → (B, vocab) logits that ``generate`` runs or captures."""
         return self.decode_step(tok, cache)

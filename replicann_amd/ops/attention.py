@@ -233,3 +233,60 @@ def attention_decode(q, k, v, mask=None, scale=None, *, lens=None):
         if m is None or (m.numel() == Tk and m.dtype == torch.float32 and m.is_contiguous()):
             return _ext.ops().attn_decode(q, k, v, m, float(scale))
     return attention(q, k, v, scale=scale, bias=mask)
+
+
+# the window kernel for the shapes it takes (a bench / test hook, not an env knob: False runs the composed
+# path on the GPU too — scripts/decode_bench.py --speculative times the kernel against it)
+WINDOW_NATIVE = True
+
+
+def attention_window(qkv, kv, pos, scale=None):
+    """T new tokens per batch row against a KV cache, each row at its own position, the append
+    included — qkv (B, T, 3, H, D) the packed projection output, kv (B, L, 2, H, D) the layer's cache
+    buffer (written in place), pos (B,) int32 / int64 on qkv's device: row b's first write row,
+    clamped to [0, L] → (B, T, H, D).  Inference only.
+
+    Row b: window rows i with pos[b] + i < L are written to ``kv[b, pos[b] + i]`` (K and V, bit for
+    bit; rows that do not fit are skipped and nothing else changes), and query i attends cache rows
+    0 .. pos[b]-1 and window rows 0 .. i.  Cache rows at or past pos[b] are never read — the window's
+    keys / values come from ``qkv`` — so stale or unwritten rows may hold anything.
+
+    On the GPU at head size 64, T <= 16 and L <= 1024 with grad off this is one launch of
+    csrc/kernels/attention_window.hip.  Otherwise (CPU tensors, other head sizes, larger T) it is
+    composed from existing ops with the same semantics: the row index pos + arange(T) is clamped to L-1
+    before any indexed write or gather (no device-side index assert is possible; the rows the clamp
+    folds onto L-1 all carry that row's final content), and the attention runs over a scratch copy of
+    the cache views with every row at or past pos zeroed, followed by the window's own T rows, under a
+    (B, T, L + T) bias built from pos."""
+    B, T, three, H, D = qkv.shape
+    L = kv.shape[1]
+    if three != 3 or kv.shape != (B, L, 2, H, D):
+        raise ValueError(f"attention_window: qkv (B, T, 3, H, D) and kv (B, L, 2, H, D) expected, got "
+                         f"{tuple(qkv.shape)} and {tuple(kv.shape)}")
+    if pos.shape != (B,) or pos.dtype not in (torch.int32, torch.int64) or pos.device != qkv.device:
+        raise ValueError(f"attention_window: pos must be ({B},) int32 / int64 on {qkv.device}, got "
+                         f"{tuple(pos.shape)} {pos.dtype} on {pos.device}")
+    if scale is None:
+        scale = D ** -0.5
+    if (WINDOW_NATIVE and _ext.use_native(qkv) and D == 64 and T <= 16 and L <= 1024
+            and not torch.is_grad_enabled()):
+        _ext.ops()  # the library is loaded
+        return torch.ops.replicann_decode.attn_window(qkv, kv, pos.contiguous(), float(scale))
+    dev = qkv.device
+    p = pos.long().clamp(0, L).view(B, 1)
+    i = torch.arange(T, device=dev).view(1, T)
+    rows = (p + i).clamp(max=L - 1)  # (B, T) in range whatever pos holds
+    # a row that does not fit lands on L-1 with what L-1 ends up holding: the window row pos + i' = L-1
+    # if there is one, else the buffer's own row (pos == L), so duplicates of an index agree
+    src = rows - p  # <= i; -1: no window row lands there
+    wide = (B, T, 2, H, D)
+    new = qkv[:, :, 1:3].gather(1, src.clamp(min=0).view(B, T, 1, 1, 1).expand(wide))
+    at = rows.view(B, T, 1, 1, 1).expand(wide)
+    kv.scatter_(1, at, torch.where((src >= 0).view(B, T, 1, 1, 1), new, kv.gather(1, at)))
+    # keys: cache rows < pos (the others zeroed: a NaN there must not reach 0 · v), then the window's own rows
+    live = (torch.arange(L, device=dev).view(1, L) < p).view(B, L, 1, 1)
+    k = torch.cat([torch.where(live, kv[:, :, 0], torch.zeros((), dtype=kv.dtype, device=dev)), qkv[:, :, 1]], 1)
+    v = torch.cat([torch.where(live, kv[:, :, 1], torch.zeros((), dtype=kv.dtype, device=dev)), qkv[:, :, 2]], 1)
+    open_ = torch.cat([live.view(B, 1, L).expand(B, T, L), (i.view(1, 1, T) <= i.view(1, T, 1)).expand(B, T, T)], 2)
+    bias = torch.zeros(B, T, L + T, device=dev).masked_fill_(~open_, float("-inf"))
+    return attention(qkv[:, :, 0], k, v, scale=scale, bias=bias)

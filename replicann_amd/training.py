@@ -481,6 +481,13 @@ def eval_main(argv=None):
     return out
 
 
+def _spec_report(stats):
+    """What ``generate(draft=..., stats=stats)`` recorded, for the JSON line (nothing without a draft)."""
+    if not stats:
+        return {}
+    return {"rounds": stats["rounds"], "drafted": stats["drafted"].tolist(), "accepted": stats["accepted"].tolist()}
+
+
 def generate_main(argv=None):
     """``python -m replicann generate``: sample continuations from a GPT-2 model — random init, or a
     checkpoint written by ``train(checkpoint=...)`` — with the KV cache and the hipGraph-replayed
@@ -506,9 +513,14 @@ def generate_main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default=None)
     ap.add_argument("--model-kwargs", type=json.loads, default={})
+    ap.add_argument("--draft-model", default=None,
+                    help="speculative decoding: a smaller GPT-2 model that proposes --draft-k tokens a round "
+                         "(greedy only: --temperature 0)")
+    ap.add_argument("--draft-checkpoint", default=None)
+    ap.add_argument("--draft-k", type=int, default=4)
     a = ap.parse_args(argv)
-    if not a.model.startswith("gpt2"):
-        raise SystemExit(f"generate: {a.model} is not an autoregressive GPT-2 model")
+    if not a.model.startswith("gpt2") or not (a.draft_model or "gpt2").startswith("gpt2"):
+        raise SystemExit(f"generate: {a.model} / {a.draft_model} is not an autoregressive GPT-2 model")
     from .utils.checkpoint import load_checkpoint
     dev = torch.device(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     torch.manual_seed(a.seed)
@@ -520,6 +532,16 @@ def generate_main(argv=None):
         from .tuning import load_committed
         load_committed(a.model)
         model = model.to(torch.bfloat16)
+    spec, stats = {}, {}
+    if a.draft_model:
+        draft = build_model(a.draft_model)
+        if a.draft_checkpoint:
+            load_checkpoint(a.draft_checkpoint, draft, restore_rng=False, allow_world_change=True)
+        draft = draft.to(dev)
+        if dev.type == "cuda":
+            load_committed(a.draft_model)
+            draft = draft.to(torch.bfloat16)
+        spec = dict(draft=draft, draft_k=a.draft_k, stats=stats)
     gen = torch.Generator(device=dev).manual_seed(a.seed)
     if a.sampler == "native" and dev.type == "cuda":  # the device seed stream takes the generator's place
         from .ops import rng
@@ -534,14 +556,14 @@ def generate_main(argv=None):
         t0 = time.perf_counter()
         rows = model.generate_batch([torch.tensor(p, dtype=torch.long) for p in prompts], a.new,
                                     temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, generator=gen,
-                                    eos_token_id=a.eos, pad_token_id=a.pad, sampler=a.sampler)
+                                    eos_token_id=a.eos, pad_token_id=a.pad, sampler=a.sampler, **spec)
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
         new = [r[len(p):].tolist() for r, p in zip(rows, prompts)]
         res = {"model": a.model, "tokens": new, "prompt_lens": [len(p) for p in prompts],
                "lengths": [int(r.numel()) for r in rows], "new_tokens": a.new, "seconds": round(dt, 4),
-               "tokens_per_s": round(sum(map(len, new)) / dt, 1)}
+               "tokens_per_s": round(sum(map(len, new)) / dt, 1), **_spec_report(stats)}
         print(json.dumps(res))
         return res
     if prompts:
@@ -550,12 +572,13 @@ def generate_main(argv=None):
         ids = torch.randint(0, model.config.vocab_size, (a.batch_size, a.prompt_len))
     t0 = time.perf_counter()
     out = model.generate(ids.to(dev), a.new, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, generator=gen,
-                         sampler=a.sampler)
+                         sampler=a.sampler, **spec)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     res = {"model": a.model, "tokens": out[:, ids.shape[1]:].tolist(), "prompt_len": ids.shape[1],
-           "new_tokens": a.new, "seconds": round(dt, 4), "tokens_per_s": round(out.shape[0] * a.new / dt, 1)}
+           "new_tokens": a.new, "seconds": round(dt, 4), "tokens_per_s": round(out.shape[0] * a.new / dt, 1),
+           **_spec_report(stats)}
     print(json.dumps(res))
     return res
 

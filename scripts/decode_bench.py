@@ -22,9 +22,22 @@ alternated in one process, three rounds.  One JSON line per timed run, then per 
 with the median ms per decode step of each and the torch / native ratio.
 
     python scripts/decode_bench.py --sample
+
+``--speculative``: what a round of speculative decoding costs, GPT-2-small drafting for GPT-2-medium
+(``--model`` / ``--draft-model``), at batch 1, 16 and 64 after a prompt of ``--prompt`` tokens.  Per batch,
+alternated in one process over three rounds of captured-graph replays: the target's and the draft's
+ragged one-token step, and the target's window step at T = 5 and T = 9 on the window kernel and on
+the composed path (the general attention under a (B, T, L + T) bias).  Then the per-layer kernel
+times of ``attn_window`` against the one-query ``attn_decode``, the break-even mean accepted length
+(at which a round of draft_k + 1 draft steps and one window step costs as much as the tokens it
+yields cost one by one), and ``generate`` end to end with and without the draft — on RANDOM-INIT
+weights, whose acceptance says nothing about trained models.  Every line is also appended to ``--out``.
+
+    python scripts/decode_bench.py --speculative --out profiles/decode_speculative.txt
 """
 
 import argparse
+import importlib
 import json
 import os
 import sys
@@ -122,6 +135,119 @@ def sample(m, model, batches, prompt=128, new=128, rounds=3):
                           "torch_over_native": round(med["torch"] / med["native"], 4)}), flush=True)
 
 
+def _replay_ms(graph, n):
+    t, _ = _timed(lambda: [graph.replay() for _ in range(n)])
+    return t / n * 1e3
+
+
+def _op_us(fn, calls=20, replays=10):
+    """µs per call of ``fn`` inside a captured graph of ``calls`` of them (no launch gaps from the host)."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(calls):
+            fn()
+    g.replay()
+    return _replay_ms(g, replays) / calls * 1e3
+
+
+def speculative(m, d, names, batches, out_path, prompt=128, new=128, rounds=3, replays=30):
+    from replicann_amd import ops
+    from replicann_amd.models import decoding
+    from replicann_amd.models.decoding import KVCache
+    A = importlib.import_module("replicann_amd.ops.attention")  # the module: ops.attention is the function
+    dev = torch.device("cuda")
+    sink = open(out_path, "a") if out_path else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    emit({"bench": "speculative decoding", "target": names[0], "draft": names[1], "prompt": prompt, "dtype": "bf16",
+          "weights": "random init", "replays_per_timing": replays, "rounds": rounds})
+    Ts = (5, 9)
+    for B in batches:
+        idx = torch.randint(0, m.config.vocab_size, (B, prompt), device=dev)
+        length = -(-(prompt + new + max(Ts)) // decoding.DECODE_LEN_BUCKET) * decoding.DECODE_LEN_BUCKET
+        caches, graphs = {}, {}
+        for name, mod in (("target", m), ("draft", d)):
+            c = caches[name] = KVCache(mod.config.n_layer, length)
+            mod.decode_step(idx, c, lens=[prompt] * B)
+            mod.decode_step(idx[:, :1], c)  # tunes the one-token GEMM shapes outside the capture
+            c.restore((prompt, torch.full_like(c.pos_t, prompt), torch.full_like(c.pos_t, prompt + 1)))
+            graphs[f"{name} one-token step"] = (decoding.capture_step(mod, c, B)[0], c)
+        c = caches["target"]
+        for T in Ts:
+            for native in (True, False):
+                A.WINDOW_NATIVE = native
+                try:
+                    m.decode_window(idx[:, :T], c)  # tunes the window GEMM shapes
+                    graphs[f"window T={T} {'native' if native else 'composed'}"] = (decoding.capture_window(m, c, B, T)[0], c)
+                finally:
+                    A.WINDOW_NATIVE = True
+        ms = {k: [] for k in graphs}
+        for r in range(rounds):
+            for k, (g, c) in graphs.items():
+                snap = c.snapshot()
+                g.replay()
+                ms[k].append(_replay_ms(g, replays))
+                c.restore(snap)  # the one-token steps moved the position
+                emit({"batch": B, "case": k, "round": r, "ms_per_step": round(ms[k][-1], 4)})
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        summary = {"summary": "median ms per step", "batch": B, **{k: round(v, 4) for k, v in med.items()}}
+        for T in Ts:
+            comp = ms[f"window T={T} composed"]
+            gain, spread = med[f"window T={T} composed"] - med[f"window T={T} native"], max(comp) - min(comp)
+            summary[f"T={T} native gain ms"] = round(gain, 4)
+            summary[f"T={T} composed spread ms"] = round(spread, 4)
+            summary[f"T={T} kernel accepted"] = bool(gain > spread)
+            # a round: T draft steps (draft_k + 1) and one window step, against (accepted + 1) one-token target steps
+            cost = T * med["draft one-token step"] + med[f"window T={T} native"]
+            summary[f"draft_k={T - 1} break-even mean accepted"] = round(cost / med["target one-token step"] - 1, 3)
+        emit(summary)
+        # the attention kernels alone, one layer: the window kernel against the one-query kernel
+        H = m.config.n_head
+        kv = torch.randn(B, length, 2, H, 64, device=dev).bfloat16()
+        pos = torch.full((B,), prompt, device=dev)
+        with torch.no_grad():
+            q1 = torch.randn(B, 1, 3, H, 64, device=dev).bfloat16()
+            rec = {"batch": B, "cached rows": prompt, "attn_decode64_k us": round(_op_us(
+                lambda: ops.attention_decode(q1[:, :, 0], kv[:, :, 0], kv[:, :, 1], lens=pos + 1)), 2)}
+            for T in (1,) + Ts:
+                qT = torch.randn(B, T, 3, H, 64, device=dev).bfloat16()
+                rec[f"attn_window T={T} us"] = round(_op_us(lambda: ops.attention_window(qT, kv, pos)), 2)
+                A.WINDOW_NATIVE = False
+                try:
+                    rec[f"composed T={T} us"] = round(_op_us(lambda: ops.attention_window(qT, kv, pos)), 2)
+                finally:
+                    A.WINDOW_NATIVE = True
+        emit(rec)
+        del kv, graphs, caches
+        # end to end, random-init weights: the acceptance is that of two unrelated random models
+        runs = {"plain greedy": dict()}
+        for T in Ts:
+            runs[f"draft_k={T - 1}"] = dict(draft=d, draft_k=T - 1)
+        for k, kw in runs.items():
+            m.generate(idx, new, temperature=0, graph=True, **kw)  # warm-up: capture
+            stats = {}
+            total, _ = _timed(lambda: m.generate(idx, new, temperature=0, graph=True, **kw, **({"stats": stats} if kw else {})))
+            rec = {"batch": B, "end to end": k, "weights": "random init", "new_tokens": new, "total_ms": round(total * 1e3, 2),
+                   "generated_tokens_per_s": round(B * new / total, 1)}
+            if kw:
+                rec["rounds"] = stats["rounds"]
+                rec["mean accepted per drafted"] = round(float(stats["accepted"].sum()) / max(1, int(stats["drafted"].sum())), 4)
+            emit(rec)
+        m.clear_decode_graphs()
+        d.clear_decode_graphs()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2-small")
@@ -130,7 +256,12 @@ def main():
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--ragged", action="store_true", help="uniform against ragged decode step (see above)")
     ap.add_argument("--sample", action="store_true", help="sampler='torch' against sampler='native' (see above)")
+    ap.add_argument("--speculative", action="store_true", help="the cost of a speculative round (see above)")
+    ap.add_argument("--draft-model", default="gpt2-small")
+    ap.add_argument("--out", default="", help="--speculative: also append every line to this file")
     a = ap.parse_args()
+    if a.speculative and a.model == "gpt2-small":
+        a.model = "gpt2-medium"  # the default pair: small drafts for medium
     from replicann_amd import _ext
     from replicann_amd.models.blocks import KVCache
     from replicann_amd.training import build_model
@@ -144,6 +275,16 @@ def main():
     for p in m.parameters():
         p.data = p.data.to(torch.bfloat16)
     m.eval()
+    if a.speculative:
+        load_committed(a.draft_model)
+        torch.manual_seed(1)
+        d = build_model(a.draft_model).to(dev)
+        for p in d.parameters():
+            p.data = p.data.to(torch.bfloat16)
+        d.eval()
+        with torch.no_grad():
+            return speculative(m, d, (a.model, a.draft_model), [int(b) for b in a.batches.split(",")], a.out,
+                               prompt=a.prompt, new=a.new)
     if a.ragged:
         return ragged(m, a.model, prompt=a.prompt, new=a.new)
     if a.sample:
