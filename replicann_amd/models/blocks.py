@@ -33,7 +33,8 @@ class Linear(nn.Module):
     """nn.Linear-compatible parameters (weight (out, in), bias (out,)) on the MFMA GEMM.
 
     ``fp8=True`` runs the forward GEMM in fp8 e4m3 with delayed scaling (ops.fp8.Fp8State);
-    the backward is the bf16 one either way."""
+    its backward then takes the fp8 weight / data gradient GEMMs per ``Fp8State.wgrad`` / ``dgrad`` (e5m2
+    dY against the e4m3 operands the forward kept) on the shapes they take, and the bf16 ones otherwise."""
 
     def __init__(self, in_features, out_features, bias=True, std=0.02, fp8=False):
         super().__init__()

@@ -4,9 +4,10 @@
 GEMM in fp8: activations and weights are quantised per tensor (delayed scaling,
 see :class:`Fp8State`), multiplied by ``v_mfma_scale_f32_16x16x128_f8f6f4`` at
 twice the bf16 MFMA rate, and the two tensor scales are folded into the epilogue
-alpha together with bias / GELU / residual.  The backward is the bf16 one (bf16
-master weight, bf16 gradients, fused activation-backward / bias reductions), the
-recipe used for "fp8 weights" training in BASELINE.json's GPT-2-medium config.
+alpha together with bias / GELU / residual.  The backward takes the fp8 GEMMs per
+gradient (``Fp8State.wgrad`` / ``dgrad``: e5m2 dY against the e4m3 operands the
+forward kept, :class:`Fp8Saved`) on the shapes they take, decided once per call in
+the forward (:class:`Fp8Plan`); master weights, gradients and reductions stay bf16.
 
 CPU tensors emulate the numerics (quantise → dequantise → fp32 matmul).
 """
@@ -14,6 +15,8 @@ CPU tensors emulate the numerics (quantise → dequantise → fp32 matmul).
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
+from typing import NamedTuple
 
 import torch
 
@@ -104,6 +107,38 @@ def fp8_dgrad_ok(dy2, n_in) -> bool:
     return dy2.shape[0] > 0 and dy2.shape[1] % 16 == 0 and n_in % 16 == 0
 
 
+class Fp8Plan(NamedTuple):
+    """Which gradients of one linear call run on the fp8 GEMMs: decided in its forward, executed by its backward."""
+    wgrad: bool
+    dgrad: bool
+
+    def published(self, need_dx, need_dw):
+        """For the producer of this call's dY (``Fp8State.bwd_plan``): per gradient, "no bf16 dY is read"."""
+        return (not need_dw or self.wgrad, not need_dx or self.dgrad)
+
+
+def _bwd_plan(have_x8, have_w8, tokens, n_out, n_in, need_dx, need_dw) -> Fp8Plan:
+    """The only place the shape rules of a linear layer's fp8 backward are consulted."""
+    dy, x = SimpleNamespace(shape=(tokens, n_out)), SimpleNamespace(shape=(tokens, n_in))
+    return Fp8Plan(bool(need_dw and have_x8 and fp8_wgrad_ok(dy, x)),
+                   bool(need_dx and have_w8 and fp8_dgrad_ok(dy, n_in)))
+
+
+class Fp8Saved(NamedTuple):
+    """What ``fp8_forward(keep=True)`` kept for the backward: the e4m3 input for the weight gradient (None
+    unless ``state.wgrad``), the e4m3 weight for the data gradient (None unless ``state.dgrad``), their scales."""
+    x8: torch.Tensor | None
+    xs: torch.Tensor | None
+    w8: torch.Tensor | None
+    ws: torch.Tensor | None
+    state: Fp8State
+
+    def plan(self, tokens, n_out, n_in, need_dx, need_dw) -> Fp8Plan:
+        """A gradient of y[tokens][n_out] = x[tokens][n_in]·Wᵀ runs in fp8 when it is needed, its operand
+        was kept and the fp8 GEMM takes the shape; otherwise in bf16."""
+        return _bwd_plan(self.x8 is not None, self.w8 is not None, tokens, n_out, n_in, need_dx, need_dw)
+
+
 def fp8_dgrad(dyq, w8, ws):
     """dX = dY·W in fp8: ``dyq`` = (e5m2 dY, its scale slot) from :meth:`Fp8State.gquant`, ``w8`` the
     forward's e4m3 weight [out][in] with scale ``ws`` (read transposed by the kernel: no transposed
@@ -176,8 +211,8 @@ class Fp8State:
         self.wcache = None  # Fp8WeightCache holding this GEMM's e4m3 weight (refreshed by the optimizer)
         self._ti = None  # inference scratch slots (see roll_slot)
         self._goffer = None  # (dY tensor, its e5m2 copy) written by the producing backward kernel (attention)
-        # set by the fp8 linear's forward: (fp8 weight gradient, fp8 data gradient) its backward will take —
-        # the producer of its dY may then skip the bf16 dY altogether
+        # Fp8Plan.published of the linear's last forward, for the op consuming its output in the same forward
+        # pass (the producer of its dY), which snapshots it into its own ctx: never read at backward time
         self.bwd_plan = (False, False)
         self.grad_mode = True  # grad mode at the op's entry (autograd Functions run forward under no_grad)
 
@@ -234,6 +269,14 @@ class Fp8State:
         """A producer wrote ``dy``'s e5m2 copy ``q`` with the gradient slot (rolled, amax recorded): the
         next gquant of the same tensor returns it."""
         self._goffer = (dy, q)
+
+    def gdecline(self):
+        """No gradient of this backward runs in fp8: drop a producer's e5m2 dY (not left for a later gquant)."""
+        self._goffer = None
+
+    def plan(self, tokens, n_out, n_in, need_dx, need_dw) -> Fp8Plan:
+        """:meth:`Fp8Saved.plan` of what a ``keep=True`` forward will keep, known before it runs (all-fp8 MLP)."""
+        return _bwd_plan(self.wgrad, self.dgrad, tokens, n_out, n_in, need_dx, need_dw)
 
     def gquant(self, dy):
         """dY in e5m2 with the gradient slot: current scaling on the first call, delayed after."""
@@ -372,17 +415,17 @@ def fp8_forward(x2, weight, bias, res2, act, preact, state: Fp8State, out8: Fp8S
 
     ``out8``: the state of the fp8 GEMM that consumes this output — the epilogue then also writes
     the output in e4m3 with that state's delayed scale and hands it over (no quantisation pass).
-    ``keep``: return (y, saved) with saved = (x8, x scale, w8, w scale, state): the e4m3 operands
-    the backward's fp8 weight gradient (x8, if ``state.wgrad``) and data gradient (w8, if
-    ``state.dgrad``) read.  Scale slots a later quant() may roll are copied; the cached weight's slot
-    changes only at the optimizer step, after this backward."""
+    ``keep``: return (y, saved) with saved an :class:`Fp8Saved`: the e4m3 operands the backward's fp8
+    weight gradient (x8, if ``state.wgrad``) and data gradient (w8, if ``state.dgrad``) read.  Scale
+    slots a later quant() may roll are copied; the cached weight's slot changes only at the optimizer
+    step, after this backward."""
     xq, xs = state.quant(x2, 0)
     wq, ws = state.quant(weight.contiguous(), 1)
     y = _fp8_forward_q(x2, xq, xs, wq, ws, bias, res2, act, preact, state, out8)
     if keep:
         x_keep = (xq, xs.clone()) if state.wgrad else (None, None)
         w_keep = (wq, ws if state.w_cached else ws.clone()) if state.dgrad else (None, None)
-        return y, (*x_keep, *w_keep, state)
+        return y, Fp8Saved(*x_keep, *w_keep, state)
     return y
 
 
@@ -407,8 +450,9 @@ def _fp8_forward_q(x2, xq, xs, wq, ws, bias, res2, act, preact, state, out8):
 
 
 def linear_fp8(x, weight, bias=None, act=None, residual=None, state: Fp8State | None = None):
-    """Linear with an fp8 e4m3 forward GEMM; the backward is the bf16 linear's
-    (ops.linear: direct flat-buffer gradient accumulation, fused bias reduction)."""
+    """Linear with an fp8 e4m3 forward GEMM; its backward takes the fp8 weight / data gradient GEMMs per
+    ``state.wgrad`` / ``state.dgrad`` on the shapes they take (ops.linear._linear_grads) and is the bf16
+    linear's otherwise (direct flat-buffer gradient accumulation, fused bias reduction)."""
     from .linear import linear
     return linear(x, weight, bias, act=act, residual=residual, fp8=state if state is not None else Fp8State())
 

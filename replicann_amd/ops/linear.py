@@ -153,6 +153,45 @@ def _pick_split_k(m_out: int, n_out: int, k: int) -> int:
     return s
 
 
+def _linear_grads(plan, saved, dy, x2, weight, native, need_dx, need_dw, dyq=None, wgrad_first=False):
+    """(gx, gw) of y = x2·weightᵀ from ``dy``, each on the GEMM the forward's ``plan`` names (an
+    :class:`~replicann_amd.ops.fp8.Fp8Plan` over the kept operands ``saved``; both None: a bf16 layer).
+    dY goes to e5m2 at most once, through the state's ``gquant`` (which picks up a producer's offer) unless
+    the caller made it already (``dyq``); a backward taking neither gradient in fp8 declines the offer.
+    gw is None when it was accumulated straight into the flat gradient buffer."""
+    use_d = saved is not None and need_dx and plan.dgrad
+    use_w = saved is not None and need_dw and plan.wgrad
+    if use_d or use_w:
+        from .fp8 import fp8_dgrad, fp8_wgrad
+        if dyq is None:
+            dyq = saved.state.gquant(dy)
+    elif saved is not None and dyq is None:
+        saved.state.gdecline()
+
+    def dgrad():
+        if use_d:  # e5m2 dY · the forward's e4m3 weight
+            return fp8_dgrad(dyq, saved.w8, saved.ws).to(x2.dtype)
+        return gemm(dy, weight, out_dtype=x2.dtype) if need_dx else None
+
+    def wgrad():
+        acc = _direct_grad(weight) if native and need_dw else None
+        if acc is not None:  # accumulate straight into the flat gradient buffer
+            if use_w:  # e5m2 dY · the forward's e4m3 input
+                fp8_wgrad(dy, saved.x8, saved.xs, saved.state, out=acc, accumulate=True, dyq=dyq)
+            else:
+                gemm(dy, x2, ta=True, split_k=-1, out=acc, accumulate=True)  # split-K chosen natively
+            _notify(weight)
+        elif use_w:
+            return fp8_wgrad(dy, saved.x8, saved.xs, saved.state, dyq=dyq).to(weight.dtype)
+        elif need_dw:
+            return gemm(dy, x2, ta=True, split_k=-1, out_dtype=weight.dtype)
+
+    if wgrad_first:
+        gw = wgrad()
+        return dgrad(), gw
+    return dgrad(), wgrad()
+
+
 class _LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, act, residual, fp8=None):
@@ -165,20 +204,19 @@ class _LinearFn(torch.autograd.Function):
         preact = None
         if act != ACT_NONE:
             preact = torch.empty(x2.shape[0], weight.shape[0], device=x.device, dtype=x.dtype)
-        ctx.x8 = None
+        ctx.saved8 = ctx.plan = None
         if fp8 is not None:
             from .fp8 import fp8_forward
             fp8.bwd_plan = (False, False)  # re-decided by every forward (a stale plan would skip a bf16 dY)
             if res2 is not None and not res2.is_contiguous():
                 res2 = res2.contiguous()
-            if fp8.fp8_bwd and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
-                # keep the e4m3 operands for the fp8 weight / data gradients
-                y, ctx.x8 = fp8_forward(x2, weight, bias, res2, act, preact, fp8, keep=True)
-                from .fp8 import fp8_dgrad_ok, fp8_wgrad_ok
-                dy_meta = torch.empty((x2.shape[0], weight.shape[0]), device="meta")
-                # which gradients the backward will take in fp8 (then nothing reads dY in bf16 there)
-                fp8.bwd_plan = (not ctx.needs_input_grad[1] or (ctx.x8[0] is not None and fp8_wgrad_ok(dy_meta, ctx.x8[0])),
-                                not ctx.needs_input_grad[0] or (ctx.x8[2] is not None and fp8_dgrad_ok(dy_meta, weight.shape[1])))
+            need_dx, need_dw = ctx.needs_input_grad[:2]
+            if fp8.fp8_bwd and (need_dx or need_dw):
+                # keep the e4m3 operands for the fp8 weight / data gradients, and decide here which of
+                # them the backward takes in fp8 (then nothing reads dY in bf16 there)
+                y, ctx.saved8 = fp8_forward(x2, weight, bias, res2, act, preact, fp8, keep=True)
+                ctx.plan = ctx.saved8.plan(x2.shape[0], weight.shape[0], weight.shape[1], need_dx, need_dw)
+                fp8.bwd_plan = ctx.plan.published(need_dx, need_dw)
             else:
                 y = fp8_forward(x2, weight, bias, res2, act, preact, fp8)
         elif native:
@@ -202,7 +240,7 @@ class _LinearFn(torch.autograd.Function):
         if not gy2.is_contiguous():
             gy2 = gy2.contiguous()
         native = _ext.use_native(gy2)
-        gx = gw = gb = None
+        gb = None
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
         if want_b and getattr(bias, "_rn_bias_done", False):
             # the downstream LayerNorm backward already accumulated Σ_rows gy into bias.grad
@@ -213,30 +251,10 @@ class _LinearFn(torch.autograd.Function):
             dh, db = _ext.ops().bias_act_grad(gy2, preact if ctx.act != ACT_NONE else None, ctx.act, want_b, db_acc)
         else:
             dh, db = bias_act_grad(gy2, preact, ctx.act, want_b)
-        sv, dyq = _fp8_bwd_operands(ctx, dh, weight)
-        if ctx.needs_input_grad[0]:
-            if dyq is not None and sv[2] is not None:  # fp8 data gradient: e5m2 dY · the e4m3 weight
-                from .fp8 import fp8_dgrad
-                gx = fp8_dgrad(dyq, sv[2], sv[3]).to(x2.dtype).reshape(ctx.shp)
-            else:
-                gx = gemm(dh, weight, out_dtype=x2.dtype).reshape(ctx.shp)
-        if ctx.needs_input_grad[1]:
-            w_acc = _direct_grad(weight) if native else None
-            if sv is not None and sv[0] is not None and _fp8_wgrad_ok(dh, sv[0]):
-                # fp8 weight gradient: e5m2 dY · the forward's e4m3 input
-                from .fp8 import fp8_wgrad
-                x8, xs, st = sv[0], sv[1], sv[4]
-                if w_acc is not None:
-                    fp8_wgrad(dh, x8, xs, st, out=w_acc, accumulate=True, dyq=dyq)
-                    _notify(weight)
-                else:
-                    gw = fp8_wgrad(dh, x8, xs, st, dyq=dyq).to(weight.dtype)
-            elif w_acc is not None:  # accumulate straight into the flat gradient buffer
-                gemm(dh, x2, ta=True, split_k=-1, out=w_acc, accumulate=True)
-                _notify(weight)
-            else:
-                gw = gemm(dh, x2, ta=True, split_k=-1, out_dtype=weight.dtype)  # split-K chosen natively
-        ctx.x8 = None
+        saved, ctx.saved8 = ctx.saved8, None
+        gx, gw = _linear_grads(ctx.plan, saved, dh, x2, weight, native, *ctx.needs_input_grad[:2])
+        if gx is not None:
+            gx = gx.reshape(ctx.shp)
         if want_b:
             if db_acc is not None:
                 _notify(bias)
@@ -312,46 +330,6 @@ def _bias_grad(g2, bias, native):
     return db.to(bias.dtype)
 
 
-def _fp8_wgrad_ok(dy2, x8):
-    from .fp8 import fp8_wgrad_ok
-    return fp8_wgrad_ok(dy2, x8)
-
-
-def _fp8_bwd_operands(ctx, dy2, weight):
-    """(saved, dyq): the fp8 forward's kept operands (x8, xs, w8, ws, state) and dY quantised ONCE
-    to e5m2 for whichever of the fp8 data / weight gradients applies (None when neither does)."""
-    sv = ctx.x8
-    ctx.x8 = None
-    if sv is None:
-        return None, None
-    from .fp8 import fp8_dgrad_ok
-    use_d = sv[2] is not None and ctx.needs_input_grad[0] and fp8_dgrad_ok(dy2, weight.shape[1])
-    use_w = sv[0] is not None and ctx.needs_input_grad[1] and _fp8_wgrad_ok(dy2, sv[0])
-    if not (use_d or use_w):
-        return sv, None
-    return sv, sv[4].gquant(dy2)
-
-
-def _wgrad(g2, x2, weight, native, x8=None, dyq=None):
-    """Weight gradient g2ᵀ·x2 into the flat gradient view (or returned).  ``x8``: (e4m3 x2, its scale,
-    Fp8State) kept by an fp8 forward → the fp8 weight-gradient GEMM (e5m2 g2, or ``dyq`` if the data
-    gradient already quantised it)."""
-    if x8 is not None and x8[0] is not None and _fp8_wgrad_ok(g2, x8[0]):
-        from .fp8 import fp8_wgrad
-        acc = _direct_grad(weight) if native else None
-        if acc is not None:
-            fp8_wgrad(g2, x8[0], x8[1], x8[2], out=acc, accumulate=True, dyq=dyq)
-            _notify(weight)
-            return None
-        return fp8_wgrad(g2, x8[0], x8[1], x8[2], dyq=dyq).to(weight.dtype)
-    acc = _direct_grad(weight) if native else None
-    if acc is not None:
-        gemm(g2, x2, ta=True, split_k=-1, out=acc, accumulate=True)
-        _notify(weight)
-        return None
-    return gemm(g2, x2, ta=True, split_k=-1, out_dtype=weight.dtype)
-
-
 class _MLPFn(torch.autograd.Function):
     """One autograd node for the whole MLP so the activation backward runs in the
     epilogue of the second layer's dgrad GEMM:  dH = (dY·W2) ⊙ act'(pre)  — the
@@ -363,99 +341,88 @@ class _MLPFn(torch.autograd.Function):
         x2 = x.reshape(-1, shp[-1]).contiguous()
         res2 = residual.reshape(-1, w2.shape[0]).contiguous() if residual is not None else None
         ops = _ext.ops()
+        nig = ctx.needs_input_grad
+        # (tokens, n_out, n_in) of the two layers; layer 2's data gradient dU is always computed
+        dims1, dims2 = (x2.shape[0], w1.shape[0], w1.shape[1]), (x2.shape[0], w2.shape[0], w1.shape[0])
+        need1, need2 = (nig[0], nig[1]), (True, nig[3])
         pre = torch.empty(x2.shape[0], w1.shape[0], device=x.device, dtype=x.dtype)
-        ctx.x8 = (None, None)
-        ctx.pre_is_h = False
-        if fp8 is not None:  # re-decided by every forward (a stale plan would skip a bf16 dY)
-            for st in fp8:
+        sv1 = sv2 = None
+        if fp8 is not None:  # (state of layer 1, state of layer 2 or None): e4m3 forward GEMMs
+            from .fp8 import fp8_forward
+            f1, f2 = fp8
+            for st in fp8:  # re-decided by every forward (a stale plan would skip a bf16 dY)
                 if st is not None:
                     st.bwd_plan = (False, False)
-        if fp8 is not None and _MLPFn._fp8_keep_h(ctx, x2, w1, w2, act, fp8):
+        ctx.pre_is_h = fp8 is not None and f2 is not None and _MLPFn._fp8_keep_h(
+            act, f2, f1.plan(*dims1, *need1), f2.plan(*dims2, *need2), nig, dims1[1], x2.device)
+        if ctx.pre_is_h:
             # the all-fp8 MLP (both layers' fp8 gradients, fused backward): c_fc on the one-wave-per-SIMD
             # fp8 GEMM writes h = x·W1ᵀ + b1 only, ONE pass makes e4m3(gelu(h)) for the MLP c_proj
             # (ops gelu_q8, the consumer's delayed scale), and the backward re-derives gelu'(h) inside its
             # fused e5m2 pass: gelu(h) / gelu'(h) are never written in bf16
-            from .fp8 import fp8_forward
-            h, sv1 = fp8_forward(x2, w1, b1, None, ACT_NONE, None, fp8[0], keep=True)
-            slot = fp8[1].roll_slot(0)
-            fp8[1].offer(h, ops.gelu_q8(h, slot), slot)
-            fp8[1].bwd_plan = (True, True)  # the fused backward takes dY in e5m2 (a producer may offer it)
-            y, sv2 = fp8_forward(h, w2, b2, res2, ACT_NONE, None, fp8[1], keep=True)
-            ctx.x8 = (sv1, sv2)
-            ctx.pre_is_h = True
-            ctx.save_for_backward(x2, w1, h, h, w2)  # (pre = h; "u" only lends its shape to the backward)
-            ctx.b1, ctx.b2, ctx.act, ctx.shp, ctx.has_res = b1, b2, act, shp, residual is not None
-            return y.reshape(*shp[:-1], w2.shape[0])
-        if fp8 is not None:  # (state of layer 1, state of layer 2 or None): e4m3 forward GEMMs
-            from .fp8 import fp8_forward
+            h, sv1 = fp8_forward(x2, w1, b1, None, ACT_NONE, None, f1, keep=True)
+            slot = f2.roll_slot(0)
+            f2.offer(h, ops.gelu_q8(h, slot), slot)
+            f2.bwd_plan = (True, True)  # the fused backward takes dY in e5m2 (a producer may offer it)
+            y, sv2 = fp8_forward(h, w2, b2, res2, ACT_NONE, None, f2, keep=True)
+            pre = u = h  # ("u" only lends its shape to the backward)
+        elif fp8 is not None:
             # layer 2's e4m3 input comes out of layer 1's epilogue (its delayed scale permitting)
             # the e4m3 operands are kept for the fp8 weight gradients and layer 1's fp8 data gradient
             # (layer 2's data gradient carries the fused activation backward: bf16)
-            if (ctx.needs_input_grad[1] and fp8[0].wgrad) or (ctx.needs_input_grad[0] and fp8[0].dgrad):
-                u, sv = fp8_forward(x2, w1, b1, None, _MLP_FWD_ACT[act], pre, fp8[0], out8=fp8[1], keep=True)
-                ctx.x8 = (sv, None)
+            if (nig[1] and f1.wgrad) or (nig[0] and f1.dgrad):
+                u, sv1 = fp8_forward(x2, w1, b1, None, _MLP_FWD_ACT[act], pre, f1, out8=f2, keep=True)
             else:
-                u = fp8_forward(x2, w1, b1, None, _MLP_FWD_ACT[act], pre, fp8[0], out8=fp8[1])
-            if fp8[1] is not None and ((ctx.needs_input_grad[3] and fp8[1].wgrad) or fp8[1].dgrad):
+                u = fp8_forward(x2, w1, b1, None, _MLP_FWD_ACT[act], pre, f1, out8=f2)
+            if f2 is not None and ((nig[3] and f2.wgrad) or f2.dgrad):
                 # (the e4m3 weight also for layer 2's fp8 data gradient: see _MLPFn._fp8_backward)
-                y, sv2 = fp8_forward(u, w2, b2, res2, ACT_NONE, None, fp8[1], keep=True)
-                ctx.x8 = (ctx.x8[0], sv2)
-            elif fp8[1] is not None:
-                y = fp8_forward(u, w2, b2, res2, ACT_NONE, None, fp8[1])
+                y, sv2 = fp8_forward(u, w2, b2, res2, ACT_NONE, None, f2, keep=True)
+            elif f2 is not None:
+                y = fp8_forward(u, w2, b2, res2, ACT_NONE, None, f2)
             else:
                 y = ops.gemm(u, w2, False, True, b2, res2, ACT_NONE, None, None, False, 0, False, None, -1)
         else:
             u = ops.gemm(x2, w1, False, True, b1, None, _MLP_FWD_ACT[act], pre, None, False, 0, False, None, -1)
             y = ops.gemm(u, w2, False, True, b2, res2, ACT_NONE, None, None, False, 0, False, None, -1)
+        # each layer's plan from what its forward kept: the backward executes them
+        p1 = sv1.plan(*dims1, *need1) if sv1 is not None else None
+        p2 = sv2.plan(*dims2, *need2) if sv2 is not None else None
+        ctx.saved8, ctx.plans = (sv1, sv2), (p1, p2)
+        ctx.fused = _MLPFn._fp8_fusable(act, p1, p2, nig, dims1[1])
         ctx.save_for_backward(x2, w1, pre, u, w2)
         ctx.b1, ctx.b2, ctx.act, ctx.shp, ctx.has_res = b1, b2, act, shp, residual is not None
         return y.reshape(*shp[:-1], w2.shape[0])
 
     @staticmethod
-    def _fp8_keep_h(ctx, x2, w1, w2, act, fp8):
-        """The forward may keep h instead of gelu(h) / gelu'(h) only when the backward is certain to take
-        the fused fp8 path (which reads neither): GELU, both layers fp8 with fp8 data AND weight gradients,
-        training, and the consumer's delayed scale already seeded."""
-        from .fp8 import FP8_MLP_FUSE, fp8_dgrad_ok, fp8_wgrad_ok
-        f1, f2 = fp8
-        nig = ctx.needs_input_grad
-        if not (FP8_MLP_FUSE and f2 is not None and _MLP_FWD_ACT.get(act) == ACT_GELU_D and nig[0] and nig[1] and nig[3]):
-            return False
-        if not (f1.wgrad and f1.dgrad and f2.wgrad and f2.dgrad and f2.producer_ready(x2.device) and not f2.inference()):
-            return False
-        M, N = x2.shape[0], w1.shape[0]
-        probe = x2.new_empty((M, N))  # (shape only)
-        dy_probe = x2.new_empty((M, w2.shape[0]))
-        # both weight gradients must take the fp8 GEMM too (tokens % 128): the bf16 fallback of _wgrad would
-        # read h where it needs gelu(h) (c_proj) and dU where it needs dH (c_fc) — ADVICE r5 (high)
-        return (N % 8 == 0 and fp8_dgrad_ok(probe, w1.shape[1]) and fp8_dgrad_ok(dy_probe, N)
-                and x2.shape[1] % 16 == 0 and N % 16 == 0
-                and fp8_wgrad_ok(probe, x2) and fp8_wgrad_ok(dy_probe, probe))
+    def _fp8_fusable(act, p1, p2, nig, n_hidden):
+        """:meth:`_fp8_backward` serves these plans: GELU, x and W1 need gradients, both data gradients and
+        layer 1's weight gradient on the fp8 GEMMs, a hidden width its fused e5m2 pass vectorises over."""
+        from .fp8 import FP8_MLP_FUSE
+        return bool(FP8_MLP_FUSE and p1 is not None and p2 is not None and _MLP_FWD_ACT.get(act) == ACT_GELU_D
+                    and nig[0] and nig[1] and p1.wgrad and p1.dgrad and p2.dgrad and n_hidden % 8 == 0)
 
     @staticmethod
-    def _fp8_backward(ctx, gy, gy2, x2, w1, pre, u, w2, sv1, sv2):
+    def _fp8_keep_h(act, f2, p1, p2, nig, n_hidden, device):
+        """The forward may keep h instead of gelu(h) / gelu'(h) only when the backward is certain to take the
+        fused fp8 path (which reads neither) with BOTH weight gradients on the fp8 GEMM too (the bf16 fallback
+        would read h for gelu(h) in c_proj's and dU for dH in c_fc's: ADVICE r5, high), in training, with the
+        consumer's delayed scale already seeded."""
+        return (_MLPFn._fp8_fusable(act, p1, p2, nig, n_hidden) and p2.wgrad and f2.producer_ready(device)
+                and not f2.inference())
+
+    @staticmethod
+    def _fp8_backward(ctx, gy, gy2, x2, w1, pre, u, w2, sv1, sv2, p1, p2):
         """Both layers' gradients in fp8 with the GELU backward fused into the e5m2 quantisation of
         dH: dY → e5m2 once (layer 2's dgrad + wgrad), dU = dY·W2 on the fp8 dgrad GEMM, then ONE pass
         dH8 = e5m2(dU ⊙ gelu'(h)) that also reduces layer 1's bias gradient (csrc/kernels/fp8.hip
         act_mul_bf8_k), and layer 1's fp8 dgrad / wgrad from dH8.  Replaces the bf16 dgrad GEMM with
         the multiply in its epilogue + the separate e5m2 pass over dH (profiles/gpt2m_fp8_r5g.txt).
-        Returns the gradient tuple, or None when an operand of that plan is missing."""
-        from .fp8 import FP8_MLP_FUSE, fp8_dgrad, fp8_dgrad_ok
+        Taken when the forward found the two plans fusable (``ctx.fused``)."""
         nig = ctx.needs_input_grad
-        if ctx.pre_is_h:  # the forward kept h: this path is the only one that can take it (_fp8_keep_h)
-            assert sv1 is not None and sv2 is not None and sv1[0] is not None and sv2[0] is not None
-            # ... and both weight gradients must run on the fp8 GEMM (the bf16 fallback would read h / dU)
-            assert _fp8_wgrad_ok(gy2, sv2[0]) and _fp8_wgrad_ok(u, sv1[0]), "keep-h MLP without fp8 weight gradients"
-        elif not (FP8_MLP_FUSE and nig[0] and nig[1] and _MLP_BWD_ACT[ctx.act] == ACT_MUL_BWD and sv1 is not None and sv2 is not None
-                and sv1[0] is not None and sv1[2] is not None and sv2[2] is not None
-                and fp8_dgrad_ok(gy2, w2.shape[1]) and fp8_dgrad_ok(u, w1.shape[1]) and _fp8_wgrad_ok(u, sv1[0])
-                and pre.shape[1] % 8 == 0):
-            return None
-        dyq2 = sv2[4].gquant(gy2)
-        x8_2 = (sv2[0], sv2[1], sv2[4]) if sv2[0] is not None else None
-        gw2 = _wgrad(gy2, u, w2, True, x8_2, dyq2 if x8_2 is not None else None) if nig[3] else None
+        dyq2 = sv2.state.gquant(gy2)  # one e5m2 dY for layer 2's wgrad and (after the bias reduction) dgrad
+        _, gw2 = _linear_grads(p2, sv2, gy2, u, w2, True, False, nig[3], dyq=dyq2)
         gb2 = _bias_grad(gy2, ctx.b2, True) if nig[4] else None
-        du = fp8_dgrad(dyq2, sv2[2], sv2[3])
+        du, _ = _linear_grads(p2, sv2, gy2, u, w2, True, True, False, dyq=dyq2)
         b1 = ctx.b1
         b1_acc, gb1 = None, None
         if nig[2] and b1 is not None:
@@ -463,14 +430,13 @@ class _MLPFn(torch.autograd.Function):
                 b1_acc = _direct_grad(b1)
             if b1_acc is None:
                 gb1 = torch.zeros(b1.shape, device=b1.device, dtype=torch.bfloat16)
-        dyq = sv1[4].gquant_mul(du, pre, b1_acc if b1_acc is not None else gb1, from_h=ctx.pre_is_h)
+        dyq = sv1.state.gquant_mul(du, pre, b1_acc if b1_acc is not None else gb1, from_h=ctx.pre_is_h)
         if b1_acc is not None:
             _notify(b1)
         elif gb1 is not None:
             gb1 = gb1.to(b1.dtype)
-        x8_1 = (sv1[0], sv1[1], sv1[4])
-        gw1 = _wgrad(du, x2, w1, True, x8_1, dyq)  # (du: the dH shape for the fp8 path's checks)
-        gx = fp8_dgrad(dyq, sv1[2], sv1[3])
+        # (du: the dH shape; dH itself exists only in e5m2)
+        gx, gw1 = _linear_grads(p1, sv1, du, x2, w1, True, True, True, dyq=dyq, wgrad_first=True)
         return gx.reshape(ctx.shp), gw1, gb1, gw2, gb2, None, gy if ctx.has_res else None, None
 
     @staticmethod
@@ -479,13 +445,15 @@ class _MLPFn(torch.autograd.Function):
         ops = _ext.ops()
         gy2 = gy.reshape(-1, w2.shape[0]).contiguous()
         nig = ctx.needs_input_grad
-        sv1, sv2 = ctx.x8
-        ctx.x8 = (None, None)
-        out = _MLPFn._fp8_backward(ctx, gy, gy2, x2, w1, pre, u, w2, sv1, sv2)
-        if out is not None:
-            return out
-        x8_2 = (sv2[0], sv2[1], sv2[4]) if sv2 is not None else None
-        gw2 = _wgrad(gy2, u, w2, True, x8_2) if nig[3] else None
+        (sv1, sv2), (p1, p2) = ctx.saved8, ctx.plans
+        ctx.saved8 = (None, None)
+        if ctx.pre_is_h:  # the forward kept h: only the fused backward can take it (_fp8_keep_h) ...
+            assert ctx.fused and sv1.x8 is not None and sv2.x8 is not None
+            # ... and both weight gradients must run on the fp8 GEMM (the bf16 fallback would read h / dU)
+            assert p1.wgrad and p2.wgrad, "keep-h MLP without fp8 weight gradients"
+        if ctx.fused:
+            return _MLPFn._fp8_backward(ctx, gy, gy2, x2, w1, pre, u, w2, sv1, sv2, p1, p2)
+        _, gw2 = _linear_grads(p2, sv2, gy2, u, w2, True, False, nig[3])
         gb2 = _bias_grad(gy2, ctx.b2, True) if nig[4] else None
         b1 = ctx.b1
         b1_acc = None
@@ -500,19 +468,7 @@ class _MLPFn(torch.autograd.Function):
             gb1 = None
         else:
             gb1 = _bias_grad(dh, b1, True) if nig[2] else None
-        dyq = None
-        if sv1 is not None:
-            from .fp8 import fp8_dgrad, fp8_dgrad_ok
-            use_d = sv1[2] is not None and nig[0] and fp8_dgrad_ok(dh, w1.shape[1])
-            use_w = sv1[0] is not None and nig[1] and _fp8_wgrad_ok(dh, sv1[0])
-            if use_d or use_w:  # dH in e5m2 once, for both
-                dyq = sv1[4].gquant(dh)
-        x8_1 = (sv1[0], sv1[1], sv1[4]) if sv1 is not None else None
-        gw1 = _wgrad(dh, x2, w1, True, x8_1, dyq) if nig[1] else None
-        if dyq is not None and sv1[2] is not None and nig[0]:
-            gx = fp8_dgrad(dyq, sv1[2], sv1[3])
-        else:
-            gx = ops.gemm(dh, w1, False, False, None, None, ACT_NONE, None, None, False, 0, False, None, -1)
+        gx, gw1 = _linear_grads(p1, sv1, dh, x2, w1, True, nig[0], nig[1], wgrad_first=True)
         return (gx.reshape(ctx.shp) if nig[0] else None, gw1, gb1, gw2, gb2, None,
                 gy if ctx.has_res else None, None)
 

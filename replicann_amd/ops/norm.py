@@ -39,9 +39,9 @@ class _LayerNormFn(torch.autograd.Function):
     linear's backward sees ``_rn_bias_done`` and skips its own bias pass.
 
     ``producer_fp8``: the :class:`~replicann_amd.ops.fp8.Fp8State` of that linear when it is an fp8 layer whose
-    backward takes dY in e5m2 (``bwd_plan``): the backward kernel then also writes dx in e5m2 with that layer's
-    delayed gradient scale and offers it (``Fp8State.goffer``), so the linear needs no quantisation pass over
-    its dY (``FP8_LN_Q8``).
+    backward takes dY in e5m2 (its ``bwd_plan``, snapshotted into the ctx by this forward): the backward kernel
+    then also writes dx in e5m2 with that layer's delayed gradient scale and offers it (``Fp8State.goffer``),
+    so the linear needs no quantisation pass over its dY (``FP8_LN_Q8``).
     """
 
     @staticmethod
@@ -62,6 +62,9 @@ class _LayerNormFn(torch.autograd.Function):
         ctx.bias_ref = bias
         ctx.producer_bias = producer_bias if residual is None else None
         ctx.producer_fp8 = producer_fp8 if residual is None else None
+        # the plan that linear's forward (already run: x is its output) published for THIS call — a later
+        # forward of the same layer overwrites Fp8State.bwd_plan before this backward runs
+        ctx.plan8 = tuple(producer_fp8.bwd_plan) if ctx.producer_fp8 is not None else (False, False)
         ctx.has_res = residual is not None
         ctx.has_bias = bias is not None
         ctx.shp = shp
@@ -90,7 +93,7 @@ class _LayerNormFn(torch.autograd.Function):
         # backward planned in fp8)
         pf = ctx.producer_fp8
         q8 = slot = None
-        if (pf is not None and FP8_LN_Q8 and pf.g_ready and any(pf.bwd_plan) and pf.gt is not None
+        if (pf is not None and FP8_LN_Q8 and pf.g_ready and any(ctx.plan8) and pf.gt is not None
                 and pf.gt.device == gy2.device):
             slot = pf.gslot(gy2.device)
             q8 = torch.empty(gy2.shape, dtype=torch.uint8, device=gy2.device)

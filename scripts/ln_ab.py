@@ -41,7 +41,7 @@ def main():
         step()
     e1.record()
     torch.cuda.synchronize()
-    print(json.dumps({"op": "ln_fwd" if fwd_only else "ln_fwd_bwd", "M": M, "E": E, "waves": os.environ.get("REPLICANN_LN_BWD_WAVES", "default"),
+    print(json.dumps({"op": "ln_fwd" if fwd_only else "ln_fwd_bwd", "M": M, "E": E,
                       "ms": round(e0.elapsed_time(e1) / 20, 4)}), flush=True)
 
 

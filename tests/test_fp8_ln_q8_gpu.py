@@ -55,6 +55,63 @@ def _step_grads(cuda, ln_q8, steps=3):
     return m, [flat.grad.clone()]
 
 
+def _linear_ln_backward(cuda, wgrad, token_counts):
+    """An fp8 Linear(128, 128) feeding a LayerNorm wired as PreLNBlock wires a projection to the next LayerNorm
+    (``producer_bias`` / ``producer_fp8``), fp8 weight gradient per ``wgrad``, data gradient in bf16.  One warm-up
+    forward/backward at 256 tokens seeds the delayed gradient scale; then one forward per entry of
+    ``token_counts`` and ONE backward on the summed losses.  Returns (state, gradient slot after the warm-up,
+    gradient slot after the backward, weight gradient, the inputs' gradients)."""
+    from replicann_amd.models import blocks
+    from replicann_amd.utils.flat import FlatParams
+
+    torch.manual_seed(0)
+    net = torch.nn.Module()
+    net.lin, net.ln = blocks.Linear(128, 128, fp8=True), blocks.LayerNorm(128)
+    net.to(cuda)
+    for p in net.parameters():
+        p.data = p.data.to(torch.bfloat16)
+    st = net.lin.fp8_state
+    st.wgrad, st.dgrad = wgrad, False
+    flat = FlatParams(net)
+
+    def call(n, seed):  # the same n and seed: the same data, whatever ran before
+        gen = torch.Generator(device=cuda).manual_seed(seed)
+        x = torch.randn(n, 128, device=cuda, generator=gen).bfloat16().requires_grad_()
+        g = torch.randn(n, 128, device=cuda, generator=gen)
+        y, _ = net.ln(net.lin(x), return_sum=True, producer_bias=net.lin.bias, producer_fp8=st)
+        return x, (y.float() * g).sum()
+
+    flat.zero_grad()
+    call(256, 1000)[1].backward()
+    warm = net.lin.fp8_gscales.clone()
+    flat.zero_grad()
+    xs, losses = zip(*[call(n, n) for n in token_counts])
+    sum(losses).backward()
+    return st, warm, net.lin.fp8_gscales.clone(), net.lin.weight.grad.clone(), [x.grad.clone() for x in xs]
+
+
+def test_two_forwards_before_one_backward_each_act_on_their_own_plan(cuda):
+    """an fp8 layer run twice before one backward (300 tokens: no fp8 weight gradient; then 256
+    tokens: fp8 weight gradient).  Each call's LayerNorm backward must act on the plan of ITS call's forward:
+    the 300-token call's must neither roll the layer's gradient scale slot nor leave an e5m2 dY on offer that
+    its linear (bf16 gradients) never takes.  Read from the layer's live state at backward time instead, both
+    calls see the 256-token plan: the slot rolls twice and an offer is left pending."""
+    st, warm, slot, gw, gxs = _linear_ln_backward(cuda, True, (300, 256))
+    assert st._offer is None and st._goffer is None
+    # the slot advanced once per call that took an fp8 gradient: exactly as after the 256-token call alone
+    st1, warm1, slot1, _, _ = _linear_ln_backward(cuda, True, (256,))
+    assert st1._offer is None and st1._goffer is None
+    assert torch.equal(warm, warm1)
+    assert not torch.equal(slot1, warm1)
+    assert torch.equal(slot, slot1), (warm, slot, slot1)
+    # and the gradients are the bf16-weight-gradient ones within the fp8 weight-gradient bound of the model test
+    # (tests/test_fp8_wgrad_gpu.py test_fp8_model_wgrad_tracks_bf16_wgrad: relative Frobenius error < 0.08)
+    _, _, _, gw0, gxs0 = _linear_ln_backward(cuda, False, (300, 256))
+    for a, b in zip([gw, *gxs], [gw0, *gxs0]):
+        assert torch.isfinite(a.float()).all()
+        assert ((a.float() - b.float()).norm() / b.float().norm()).item() < 0.08
+
+
 def test_gpt2_fp8_step_bitwise_with_layernorm_e5m2(cuda, monkeypatch):
     # the default token-embedding scatter adds float atomics in arrival order (a repeated token id's rows sum
     # in whatever order the waves land): two runs whose earlier kernels differ in timing may differ in wte's

@@ -106,6 +106,73 @@ def test_fp8_dgrad_cpu_emulation_tracks_bf16_grads():
         assert ((a - b).norm() / b.norm().clamp_min(1e-12)) < 0.15, n
 
 
+# Fp8Saved.plan, cell by cell: which gradients ("w" weight, "d" data, "-" neither) run on the fp8 GEMMs.
+# One block per (tokens, n_in, n_out); rows = (state.wgrad, state.dgrad) 00 01 10 11; columns = (need_dx,
+# need_dw) 00 01 10 11.  300 % 128 != 0: no fp8 weight gradient; 40 % 16 != 0: neither.
+_PLAN_TABLE = {
+    (256, 128, 512): ["-- -- -- --",
+                      "-- -- -d -d",
+                      "-- w- -- w-",
+                      "-- w- -d wd"],
+    (300, 128, 512): ["-- -- -- --",
+                      "-- -- -d -d",
+                      "-- -- -- --",
+                      "-- -- -d -d"],
+    (256, 128, 40): ["-- -- -- --"] * 4,
+    (300, 128, 40): ["-- -- -- --"] * 4,
+}
+
+
+def test_fp8_backward_plan_truth_table():
+    """The one place the fp8 backward's shape rules are consulted (Fp8Saved.plan) against a literal table,
+    the same answer from Fp8State.plan before the forward, a missing kept operand falling back to bf16, and
+    the published tuple keeping its "no bf16 dY read" sense (a gradient that is not needed publishes True)."""
+    from replicann_amd import ops
+    from replicann_amd.ops.fp8 import Fp8Plan, Fp8Saved, Fp8State, fp8_forward
+
+    x, w = torch.randn(8, 16), torch.randn(16, 16)
+    flags = [(False, False), (False, True), (True, False), (True, True)]
+    for (tokens, n_in, n_out), rows in _PLAN_TABLE.items():
+        for (wg, dg), row in zip(flags, rows):
+            st = Fp8State()
+            st.wgrad, st.dgrad = wg, dg
+            _, saved = fp8_forward(x, w, None, None, 0, None, st, keep=True)
+            assert isinstance(saved, Fp8Saved) and saved.state is st
+            assert (saved.x8 is not None, saved.w8 is not None) == (wg, dg)  # the keep rules
+            assert (saved.xs is not None, saved.ws is not None) == (wg, dg)
+            for (need_dx, need_dw), cell in zip(flags, row.split()):
+                want = Fp8Plan(wgrad=cell[0] == "w", dgrad=cell[1] == "d")
+                key = (tokens, n_in, n_out, wg, dg, need_dx, need_dw)
+                plan = saved.plan(tokens, n_out, n_in, need_dx, need_dw)
+                assert plan == want, key
+                assert st.plan(tokens, n_out, n_in, need_dx, need_dw) == want, key
+                assert plan.published(need_dx, need_dw) == (not need_dw or want.wgrad, not need_dx or want.dgrad)
+                # an operand that was not kept: that gradient runs in bf16, the other is unaffected
+                assert saved._replace(x8=None, xs=None).plan(tokens, n_out, n_in, need_dx, need_dw) \
+                    == Fp8Plan(False, want.dgrad), key
+                assert saved._replace(w8=None, ws=None).plan(tokens, n_out, n_in, need_dx, need_dw) \
+                    == Fp8Plan(want.wgrad, False), key
+    assert Fp8Plan(False, False).published(False, False) == (True, True)
+    assert Fp8Plan(False, False).published(True, True) == (False, False)
+    assert Fp8Plan(True, False).published(True, True) == (True, False)
+    assert Fp8Plan(False, True).published(True, False) == (True, True)
+
+    # ... and what a linear's forward publishes on its state (CPU emulation path)
+    def published(tokens, x_grad, w_grad, wg, dg):
+        st = Fp8State()
+        st.wgrad, st.dgrad = wg, dg
+        xi = torch.randn(tokens, 128, requires_grad=x_grad)
+        ops.linear(xi, torch.randn(512, 128, requires_grad=w_grad), fp8=st)
+        return st.bwd_plan
+
+    assert published(256, True, True, True, True) == (True, True)
+    assert published(300, True, True, True, True) == (False, True)
+    assert published(256, True, True, True, False) == (True, False)
+    assert published(256, False, True, True, False) == (True, True)  # dX not needed: no bf16 dY read for it
+    assert published(256, True, False, False, True) == (True, True)  # dW not needed
+    assert published(256, True, True, False, False) == (False, False)
+
+
 def test_fp8_head_slots_checkpoint_compat():
     """The fp8 LM head's slots (GPT2Config.fp8_head) are a state_dict buffer; a checkpoint written without
     them (bf16 head, or an older fp8 model) loads strictly into a head model with empty slots, and the CPU

@@ -236,7 +236,7 @@ def test_gelu_q8_and_act_mul_from_h(cuda):
 
 def test_fp8_mlp_keep_h_tracks_unfused(cuda, monkeypatch):
     """GPT-2 (tiny, fp8): the all-fp8 MLP path (h kept, gelu(h) quantised in one pass, fused GELU backward)
-    trains like the REPLICANN_FP8_MLP_FUSE=0 path (bf16 c_proj dgrad, gelu'(h) saved by the epilogue) within
+    trains like the ops.fp8.FP8_MLP_FUSE = False path (bf16 c_proj dgrad, gelu'(h) saved by the epilogue) within
     fp8 noise, with finite gradients everywhere."""
     import replicann_amd as R
     import replicann_amd.ops.fp8 as F
@@ -308,7 +308,7 @@ def test_fp8_mlp_ragged_tokens_gradients_match_unfused(cuda, monkeypatch):
 
 def test_fp8_attention_q8_dqkv_tracks_quantise_pass(cuda, monkeypatch):
     """GPT-2 (tiny, fp8, fp8 backward): the attention backward's own e5m2 dQKV (no bf16 dQKV when c_attn
-    takes both gradients in fp8) trains like the path that quantises a bf16 dQKV (REPLICANN_FP8_ATTN_Q8=0)."""
+    takes both gradients in fp8) trains like the path that quantises a bf16 dQKV (ops.attention.ATTN_Q8 = False)."""
     import importlib
 
     import replicann_amd as R
