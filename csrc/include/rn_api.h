@@ -112,7 +112,7 @@ int rn_gemm_sched_init(int dev);
 int* rn_gemm_sched_slot(int dev, hipStream_t st);
 // Workspace floats needed for a split-K launch.
 long rn_gemm_ws_floats(int M, int N, int split);
-// BM of a tile config; rows of the column-partial matrix a config writes
+// BM of a tile config; rows of the column-partial matrix a config writes (the table in gemm_plan.h)
 int rn_gemm_cfg_bm(int cfg);
 long rn_gemm_colpart_rows(int cfg, int M);
 // C[M,N] = act(alpha · op(A)[M,K] · op(B)[K,N] + bias) + res.
@@ -127,9 +127,8 @@ int rn_gemm(const void* A, const void* B, void* C, const void* bias, const void*
             int split, int out_f32, int accumulate, int cfg, hipStream_t st, float* colpart);
 
 // ------------------------------------------------------------------ gemm_skinny.hip
-// Returns -1 for what this config does not take (the caller's autotuner then skips it): a
-// transposed operand, M > 64, accumulate, activation backward, column partials, split without a
-// workspace.  ``split``: K ranges (>= 1); each is a multiple of 32 deep.
+// Returns -1 for what this config does not take (gemm_plan.h: gemm_cfg_takes(10, ...)) and for a split
+// without a workspace.  ``split``: K ranges (>= 1); each is a multiple of 32 deep.
 int rn_gemm_skinny(const void* A, const void* W, void* C, const void* bias, const void* res, void* pre, float* ws,
                    const float* alpha, int M, int N, int K, long lda, long ldw, long ldc, int trans_a, int trans_b,
                    int act, int split, int out_f32, int accumulate, const float* colpart, hipStream_t st);

@@ -45,12 +45,19 @@
 #include <mutex>
 
 #include "common.h"
+#include "gemm_plan.h"
 #include "rn_api.h"
 
 #include "gemm_pk.h"
 
 using rn_gemm_detail::GemmArgs;
 using rn_gemm_detail::BK;
+
+// gemm_plan.h spells these out (it cannot include the device headers)
+static_assert(gemm_act_bwd(ACT_RELU_BWD) && gemm_act_bwd(ACT_GELU_BWD) && gemm_act_bwd(ACT_MUL_BWD) &&
+              !gemm_act_bwd(ACT_NONE) && !gemm_act_bwd(ACT_RELU) && !gemm_act_bwd(ACT_GELU) && !gemm_act_bwd(ACT_GELU_D));
+static_assert(gemm_act_skinny(ACT_NONE) && gemm_act_skinny(ACT_RELU) && gemm_act_skinny(ACT_GELU) &&
+              gemm_act_skinny(ACT_GELU_D) && BK == 64);
 
 namespace {
 
@@ -61,10 +68,6 @@ inline long ntiles(int M, int N, int bm, int bn) { return (long)((M + bm - 1) / 
 // 2 per CU, a 256² block 1 per CU and ~13 % faster per FLOP (half the L2→LDS
 // bytes per FLOP); a launch takes ceil(tiles / resident slots) rounds.
 struct Choice { int cfg, split; };
-
-inline bool pk_ok(int N, long ldc, int out_f32, int act) {
-    return N % 8 == 0 && ldc % 8 == 0 && !(out_f32 && act != ACT_NONE);
-}
 
 inline Choice pick(int M, int N, int K, int split_req) {
     const double flop_s_cu = 2.9e12;  // effective per-CU bf16 rate of the 128² config
@@ -183,13 +186,10 @@ int* rn_gemm_sched_slot(int dev, hipStream_t st) {
 
 long rn_gemm_ws_floats(int M, int N, int split) { return split > 1 ? (long)split * M * N : 0; }
 
-int rn_gemm_cfg_bm(int cfg) { return (cfg == 0 || cfg == 3 || cfg == 5 || cfg == 9) ? 128 : 256; }
-// (cfg 9: one row per (256-row tile, wave row))
-long rn_gemm_colpart_rows(int cfg, int M) {
-    return (cfg == 9) ? 2L * ((M + 255) / 256) : (long)((M + rn_gemm_cfg_bm(cfg) - 1) / rn_gemm_cfg_bm(cfg));
-}
+int rn_gemm_cfg_bm(int cfg) { return gemm_cfg(cfg).bm; }
+long rn_gemm_colpart_rows(int cfg, int M) { return gemm_colpart_rows(cfg, M); }
 
-// The contract is in rn_api.h.  Tile configs:
+// The contract is in rn_api.h; which config takes which problem is gemm_plan.h's gemm_cfg_takes.  Tile configs:
 //   cfg: -1 auto, 0 = 128x128, 1 = 256x256 pipelined, 2 = 256x128 pipelined, 3 = 128x256,
 //        4 = 256x256 simple, 5 = 128x128 pipelined, 6 = 256x192 pipelined, 8 = 256x128 3-stage ring,
 //        9 = persistent 256x256 half-tile stream (gemm_pk.h; needs N % 8 == 0, ldc % 8 == 0)
@@ -199,17 +199,14 @@ long rn_gemm_colpart_rows(int cfg, int M) {
 int rn_gemm(const void* A, const void* B, void* C, const void* bias, const void* res, void* pre, float* ws,
             const float* alpha, int M, int N, int K, long lda, long ldb, long ldc, int trans_a, int trans_b, int act,
             int split, int out_f32, int accumulate, int cfg, hipStream_t st, float* colpart) {
-    if (K % 8 != 0) return -1;
+    const GemmProblem p{M, N, K, lda, ldb, ldc, trans_a != 0, trans_b != 0, act, out_f32 != 0, accumulate != 0,
+                        bias != nullptr, res != nullptr, alpha != nullptr, pre != nullptr, colpart != nullptr, split};
     if (cfg == 10)  // skinny-M decode GEMM (gemm_skinny.hip): its own N x K decomposition
         return rn_gemm_skinny(A, B, C, bias, res, pre, ws, alpha, M, N, K, lda, ldb, ldc, trans_a, trans_b, act,
                               split, out_f32, accumulate, colpart, st);
-    if (act_bwd(act) && (trans_a || trans_b || !pre)) return -1;  // fused act-backward: dgrad layout only
-    if (trans_a && (M % 8 != 0 || lda % 8 != 0)) return -1;
-    if (!trans_a && lda % 8 != 0) return -1;
-    if (!trans_b && (N % 8 != 0 || ldb % 8 != 0)) return -1;
-    if (trans_b && ldb % 8 != 0) return -1;
+    if (!gemm_operands_ok(p)) return -1;
     if (cfg == 11) {  // one-wave-per-SIMD persistent kernel (gemm_w1.h): x·Wᵀ, plain / bias epilogue
-        if (!trans_a && act == ACT_NONE && !accumulate && !out_f32 && split <= 1 && !colpart) {
+        if (gemm_cfg_takes(11, p, split)) {
             GemmArgs w = {};
             w.A = (const bf16*)A; w.B = (const bf16*)B; w.C = C; w.bias = (const bf16*)bias; w.alpha = alpha;
             w.res = (const bf16*)res;
@@ -223,10 +220,10 @@ int rn_gemm(const void* A, const void* B, void* C, const void* bias, const void*
     a.pre = (bf16*)pre; a.ws = ws; a.alpha = alpha; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
     if (cfg < 0 || split < 0) {
         Choice ch = pick(M, N, K, split);
-        if (cfg < 0) cfg = pk_ok(N, ldc, out_f32, act) ? 9 : ch.cfg;
+        if (cfg < 0) cfg = gemm_pk_ok(p) ? 9 : ch.cfg;
         if (split < 0) split = ch.split;
     }
-    if (cfg == 9 && !pk_ok(N, ldc, out_f32, act)) cfg = 1;  // shapes the persistent kernel does not take
+    if (cfg == 9 && !gemm_pk_ok(p)) cfg = 1;  // shapes the persistent kernel does not take
     if (cfg >= 90 && cfg < 90 + 256) {  // timing-only ablation builds of cfg 9 (wrong outputs)
 #ifndef REPLICANN_DEV
         return -1;  // not in a production library (REPLICANN_DEV=1 builds them)
@@ -238,17 +235,12 @@ int rn_gemm(const void* A, const void* B, void* C, const void* bias, const void*
         return rn_gemm_launch_pk_dbg(d, !trans_a, trans_b, cfg - 90, st) == 0 ? 0 : -1;
 #endif
     }
-    a.split = split < 1 ? 1 : split;
-    int kps = (K + a.split - 1) / a.split;
-    kps = (kps + BK - 1) / BK * BK;
-    a.k_per_split = kps;
-    a.split = (K + kps - 1) / kps;
+    a.k_per_split = gemm_k_per_split(K, split);
+    a.split = gemm_slabs(K, split);
     a.out_f32 = out_f32; a.accumulate = accumulate;
     a.colpart = colpart;
 
-    if (colpart && (!act_bwd(act) || a.split > 1 || out_f32 || N % 8 != 0 || ldc % 8 != 0 || cfg == 6 || cfg == 4 ||
-                    cfg == 3))
-        return -3;  // 256x192 (CPR 24) and the simple 256-wide configs are not wired for it
+    if (colpart && !gemm_colpart_ok(cfg, p, split)) return -3;
     const bool ak = !trans_a, bk = trans_b;
     switch (cfg) {
         case 1: rn_gemm_launch_cfg1(a, ak, bk, act, st); break;

@@ -17,6 +17,7 @@
 // Epilogue order as the tile kernels': ·alpha, +bias, activation (with the optional
 // pre-activation / gelu' store of the bf16-rounded h), +residual.
 #include "common.h"
+#include "gemm_plan.h"
 #include "rn_api.h"
 
 namespace {
@@ -162,9 +163,9 @@ void sk_launch(const SkArgs& a, int mb, hipStream_t st) {
 extern "C" int rn_gemm_skinny(const void* A, const void* W, void* C, const void* bias, const void* res, void* pre, float* ws,
                    const float* alpha, int M, int N, int K, long lda, long ldw, long ldc, int trans_a, int trans_b,
                    int act, int split, int out_f32, int accumulate, const float* colpart, hipStream_t st) {
-    if (trans_a || !trans_b || M < 1 || M > 64 || accumulate || act_bwd(act) || colpart) return -1;
-    if (K % 8 != 0 || lda % 8 != 0 || ldw % 8 != 0) return -1;
-    if (act != ACT_NONE && act != ACT_RELU && act != ACT_GELU && act != ACT_GELU_D) return -1;
+    const GemmProblem p{M, N, K, lda, ldw, ldc, trans_a != 0, trans_b != 0, act, out_f32 != 0, accumulate != 0,
+                        bias != nullptr, res != nullptr, alpha != nullptr, pre != nullptr, colpart != nullptr, split};
+    if (!gemm_cfg_takes(10, p, split)) return -1;
     SkArgs a = {};
     a.A = (const bf16*)A; a.W = (const bf16*)W; a.C = C; a.bias = (const bf16*)bias; a.res = (const bf16*)res;
     a.pre = (bf16*)pre; a.ws = ws; a.alpha = alpha; a.M = M; a.N = N; a.K = K;

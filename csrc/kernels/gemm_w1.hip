@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "gemm_plan.h"
 #include "gemm_w1.h"
 
 using namespace rn_gemm_detail;
@@ -14,12 +15,19 @@ using namespace rn_gemm_detail;
 // K, lda, ldb in BYTES (K % 128 == 0, K >= 256); ldc in elements; N % 8 == 0
 int rn_gemm_launch_w1(GemmArgs& a, int fp8, int act, hipStream_t st, bool bmn) {
     a.group_m = GROUP_M;
-    if (a.K % 128 || a.K < 256 || a.N % 8 || a.ldc % 8 || a.lda % 16 || a.ldb % 16) return -1;
-    if (act != ACT_NONE) return -1;
-    if (a.alpha && a.bias) return -1;
-    if (bmn && fp8 && (a.N % 16 || a.bias || a.res)) return -1;  // fp8 MN-contiguous B: plain / alpha epilogue
-    if (fp8 && !bmn && a.alpha) return -1;
-    if (a.res && (bmn || a.alpha || a.K / 128 < 6)) return -1;  // residual bodies: K-tiles 1-4 of >= 6
+    if (!fp8) {  // bf16: cfg 11's contract is gemm_plan.h's, in elements
+        const GemmProblem p{a.M, a.N, a.K / 2, a.lda / 2, a.ldb / 2, a.ldc, false, !bmn, act, a.out_f32 != 0,
+                            a.accumulate != 0, a.bias != nullptr, a.res != nullptr, a.alpha != nullptr, a.pre != nullptr,
+                            a.colpart != nullptr, a.split};
+        if (!gemm_cfg_takes(11, p, a.split)) return -1;
+    } else {
+        if (a.K % 128 || a.K < 256 || a.N % 8 || a.ldc % 8 || a.lda % 16 || a.ldb % 16) return -1;
+        if (act != ACT_NONE) return -1;
+        if (a.alpha && a.bias) return -1;
+        if (bmn && (a.N % 16 || a.bias || a.res)) return -1;  // fp8 MN-contiguous B: plain / alpha epilogue
+        if (!bmn && a.alpha) return -1;
+        if (a.res && (bmn || a.alpha || a.K / 128 < 6)) return -1;  // residual bodies: K-tiles 1-4 of >= 6
+    }
     a.tiles_m = (a.M + 255) / 256;
     a.tiles_n = (a.N + 255) / 256;
 #ifdef REPLICANN_DEV

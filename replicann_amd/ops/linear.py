@@ -69,7 +69,8 @@ def gemm(a, b, *, ta=False, tb=False, bias=None, residual=None, act=ACT_NONE, pr
     A, B are 2-D row-major bf16.  On CPU it is the ATen reference.
     ``accumulate`` adds into ``out`` (fp32 or bf16) instead of overwriting.
     ``alpha`` is an optional 1-element fp32 DEVICE tensor (read in the epilogue,
-    graph-safe).  ``cfg`` forces a tile config (-1 = auto; 0..3 see gemm_bf16.hip).
+    graph-safe).  ``cfg`` forces a tile config (-1 = auto; the list is above ``rn_gemm`` in
+    csrc/kernels/gemm_bf16.hip).
     """
     if _ext.use_native(a):
         return _ext.ops().gemm(a, b, ta, tb, bias, residual, act, preact, out, accumulate, split_k,
@@ -143,16 +144,6 @@ def _notify(p):
     p._rn_flat.mark_ready(p)
 
 
-def _pick_split_k(m_out: int, n_out: int, k: int) -> int:
-    tiles = math.ceil(m_out / 128) * math.ceil(n_out / 128)
-    if tiles >= 512 or k < 1024:
-        return 1
-    s = 1
-    while tiles * s < 512 and k // (s * 2) >= 512:
-        s *= 2
-    return s
-
-
 def _linear_grads(plan, saved, dy, x2, weight, native, need_dx, need_dw, dyq=None, wgrad_first=False):
     """(gx, gw) of y = x2·weightᵀ from ``dy``, each on the GEMM the forward's ``plan`` names (an
     :class:`~replicann_amd.ops.fp8.Fp8Plan` over the kept operands ``saved``; both None: a bf16 layer).
@@ -220,7 +211,7 @@ class _LinearFn(torch.autograd.Function):
             else:
                 y = fp8_forward(x2, weight, bias, res2, act, preact, fp8)
         elif native:
-            y = _ext.ops().gemm(x2, weight, False, True, bias, res2, act, preact, None, False, 0, False, None, -1)
+            y = _ext.ops().gemm(x2, weight, tb=True, bias=bias, residual=res2, act=act, preact=preact)
         else:
             y = gemm(x2, weight, tb=True, bias=bias, residual=res2, act=act, preact=preact,
                      out_dtype=x.dtype)
@@ -380,10 +371,10 @@ class _MLPFn(torch.autograd.Function):
             elif f2 is not None:
                 y = fp8_forward(u, w2, b2, res2, ACT_NONE, None, f2)
             else:
-                y = ops.gemm(u, w2, False, True, b2, res2, ACT_NONE, None, None, False, 0, False, None, -1)
+                y = ops.gemm(u, w2, tb=True, bias=b2, residual=res2)
         else:
-            u = ops.gemm(x2, w1, False, True, b1, None, _MLP_FWD_ACT[act], pre, None, False, 0, False, None, -1)
-            y = ops.gemm(u, w2, False, True, b2, res2, ACT_NONE, None, None, False, 0, False, None, -1)
+            u = ops.gemm(x2, w1, tb=True, bias=b1, act=_MLP_FWD_ACT[act], preact=pre)
+            y = ops.gemm(u, w2, tb=True, bias=b2, residual=res2)
         # each layer's plan from what its forward kept: the backward executes them
         p1 = sv1.plan(*dims1, *need1) if sv1 is not None else None
         p2 = sv2.plan(*dims2, *need2) if sv2 is not None else None
@@ -461,8 +452,7 @@ class _MLPFn(torch.autograd.Function):
             b1_acc = _direct_grad(b1)
         # dH = (dY·W2) ⊙ act'(pre); with a flat-buffer b1 its gradient Σ_rows dH comes from the
         # same GEMM's epilogue (per-tile column partials + one small reduction)
-        dh = ops.gemm(gy2, w2, False, False, None, None, _MLP_BWD_ACT[ctx.act], pre, None, False, 0, False, None, -1,
-                      b1_acc)
+        dh = ops.gemm(gy2, w2, act=_MLP_BWD_ACT[ctx.act], preact=pre, bias_grad=b1_acc)
         if b1_acc is not None:
             _notify(b1)
             gb1 = None

@@ -63,7 +63,7 @@ class _LinearXentFn(torch.autograd.Function):
         ops = _ext.ops()
         shp = h.shape
         h2 = h.reshape(-1, shp[-1]).contiguous()
-        logits = ops.gemm(h2, weight, False, True, None, None, 0, None, None, False, 0, False, None, -1)
+        logits = ops.gemm(h2, weight, tb=True)
         tg = target.reshape(-1).long().contiguous()
         loss_rows, _ = ops.xent_fwd(logits, tg, n_valid_cols, ignore_index, True)
         n = (tg != ignore_index).sum().clamp_min(1).float()
@@ -80,15 +80,15 @@ class _LinearXentFn(torch.autograd.Function):
         gh = gw = None
         if ctx.needs_input_grad[0]:
             # g/n as the epilogue alpha (fp32, before the bf16 rounding): no separate scaling pass
-            gh = ops.gemm(dlogits, weight, False, False, None, None, 0, None, None, False, 0, False, alpha, -1)
+            gh = ops.gemm(dlogits, weight, alpha=alpha)
             gh = gh.reshape(ctx.shp)
         if ctx.needs_input_grad[1]:
             acc = _direct_grad(weight)
             if acc is not None:
-                ops.gemm(dlogits, h2, True, False, None, None, 0, None, acc, True, -1, False, alpha, -1)
+                ops.gemm(dlogits, h2, ta=True, out=acc, accumulate=True, split_k=-1, alpha=alpha)
                 _notify(weight)
             else:
-                gw = ops.gemm(dlogits, h2, True, False, None, None, 0, None, None, False, -1, False, alpha, -1)
+                gw = ops.gemm(dlogits, h2, ta=True, split_k=-1, alpha=alpha)
         return gh, gw, None, None, None
 
 
@@ -126,13 +126,13 @@ class _ChunkedLinearXentFn(torch.autograd.Function):
         for r0 in range(0, M, chunk):
             r1 = min(M, r0 + chunk)
             hc, lg = h2[r0:r1], buf[: r1 - r0]
-            ops.gemm(hc, weight, False, True, None, None, 0, None, lg, False, 0, False, None, -1)
+            ops.gemm(hc, weight, tb=True, out=lg)
             rows, _ = ops.xent_fwd(lg, tg[r0:r1], n_valid_cols, ignore_index, want)
             loss += rows.sum()
             if need_h:
-                ops.gemm(lg, weight, False, False, None, None, 0, None, gh[r0:r1], False, -1, False, inv_n, -1)
+                ops.gemm(lg, weight, out=gh[r0:r1], split_k=-1, alpha=inv_n)
             if need_w:
-                ops.gemm(lg, hc, True, False, None, None, 0, None, gw, True, -1, False, inv_n, -1)
+                ops.gemm(lg, hc, ta=True, out=gw, accumulate=True, split_k=-1, alpha=inv_n)
         del buf
         ctx.save_for_backward(weight, gh, gw)
         ctx.shp = shp
@@ -186,7 +186,7 @@ class _LinearXentFp8Fn(torch.autograd.Function):
         if fp8_logits:
             logits = ops.gemm_fp8(xq, wq, xs, ws, None, None, 0, None)
         else:
-            logits = ops.gemm(h2, weight, False, True, None, None, 0, None, None, False, 0, False, None, -1)
+            logits = ops.gemm(h2, weight, tb=True)
         tg = target.reshape(-1).long().contiguous()
         q8 = torch.empty(logits.shape, dtype=torch.uint8, device=logits.device)
         loss_rows, _ = ops.xent_fwd_q8(logits, tg, n_valid_cols, ignore_index, q8)

@@ -41,10 +41,10 @@ def test_op_schemas_and_dispatch_keys_are_pinned():
     binding that moves between files must register exactly what it registered before."""
     want = set(FIXTURE.read_text().splitlines())
     got = _registered()
-    assert len(want) == 77
+    assert len(want) == 78
     assert got == want, f"missing: {sorted(want - got)}\nunexpected: {sorted(got - want)}"
     assert sum(line.endswith("| CUDA") for line in got) == 56
-    assert sum(line.endswith("| CompositeExplicitAutograd") for line in got) == 8
+    assert sum(line.endswith("| CompositeExplicitAutograd") for line in got) == 9
 
 
 def _strip_comments(text):

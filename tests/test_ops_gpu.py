@@ -197,6 +197,51 @@ def test_gemm_skinny_rejects_other_layouts(cuda):
         ops.gemm(bf(128, 64), bf(32, 64), tb=True, cfg=10)  # M > 64
 
 
+def _tune_once(call, key, cand_args):
+    """``call()`` on a key no earlier test of this file tunes (test_gemm_gelu_saved_derivative below shares
+    the second one): the tuner stores exactly one entry for it, one of the candidates gemm_plan.h lists;
+    a second call reuses it bit for bit.  Returns (output, entry)."""
+    import json
+
+    def entries():
+        table = json.loads(torch.ops.replicann.gemm_tuning_table())
+        return len(table), [e for e in table if {k: e[k] for k in key} == key]
+
+    out = call()
+    n, mine = entries()
+    assert len(mine) == 1
+    flat = torch.ops.replicann.gemm_candidates(*cand_args)
+    assert (mine[0]["cfg"], mine[0]["split"]) in list(zip(flat[0::2], flat[1::2]))
+    assert torch.equal(call(), out)
+    assert entries() == (n, mine)
+    return out, mine[0]
+
+
+def test_gemm_autotune_picks_a_listed_candidate(cuda):
+    """An eager call without cfg / split_k tunes its key once (the ragged small shape of test_gemm_layouts,
+    in no committed table)."""
+    torch.manual_seed(14)
+    M, N, K = 200, 72, 96
+    a, w, bias = bf(M, K), bf(N, K), bf(N)
+    key = dict(M=M, N=N, K=K, ta=0, tb=1, act=0, f32=0, epi=1, **{"as": 0})
+    out, _ = _tune_once(lambda: ops.gemm(a, w, tb=True, bias=bias), key,
+                        (M, N, K, False, True, 0, False, False, 0, True, False, False, False, N))
+    assert rel_err(out, a.float() @ w.float().t() + bias.float()) < 1e-2
+
+
+def test_gemm_autotune_act_backward_bias_grad(cuda):
+    """The fused activation backward with the bias gradient (key epilogue bit 16): the 256x192 config 6
+    cannot emit column partials and is not among the candidates."""
+    torch.manual_seed(15)
+    M, N, K = 520, 776, 384
+    dy, w, pre = bf(M, K), bf(K, N, scale=0.1), bf(M, N)
+    key = dict(M=M, N=N, K=K, ta=0, tb=0, act=6, f32=0, epi=16, **{"as": 0})
+    out, entry = _tune_once(lambda: torch.ops.replicann.gemm(dy, w, act=6, preact=pre, bias_grad=torch.zeros_like(w[0])),
+                            key, (M, N, K, False, False, 6, False, False, 0, False, False, False, True, N))
+    assert entry["cfg"] != 6
+    assert rel_err(out, (dy.float() @ w.float()).bfloat16().float() * pre.float()) < 1e-2
+
+
 def _gelu_grad(h):
     hf = h.float().requires_grad_()
     (g,) = torch.autograd.grad(F.gelu(hf, approximate="tanh"), hf, torch.ones_like(hf))
