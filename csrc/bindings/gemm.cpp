@@ -64,6 +64,7 @@ Tensor gemm(const Tensor& a, const Tensor& b, bool ta, bool tb, const optional<T
         TORCH_CHECK(act_bwd, "gemm bias_grad needs an activation-backward epilogue");
         CHECK_BF16(*bias_grad);
         TORCH_CHECK(bias_grad->numel() == N && bias_grad->is_contiguous());
+        TORCH_CHECK(!out_fp32, "gemm bias_grad needs a bf16 output (both reductions read bf16 rows)");
     }
     // rows: enough for every config (128-row tiles: ceil(M/128); cfg 9: 2 per 256-row tile)
     Tensor colpart = want_bg ? at::empty({2 * ((M + 255) / 256), N}, a.options().dtype(at::kFloat)) : Tensor();
@@ -131,18 +132,20 @@ Tensor gemm(const Tensor& a, const Tensor& b, bool ta, bool tb, const optional<T
     void* pre = has(preact) ? preact->data_ptr() : nullptr;
     auto launch = [&](float* colp) { return run(c, pre, ws, icfg, split, accumulate, colp); };
     int rc = launch(cp);
-    if (rc == -3) {  // this config cannot emit column partials: plain GEMM + one reduction pass over C
+    if (rc == -3) {  // this config cannot emit column partials: plain GEMM + one reduction pass over C's rows
         rc = launch(nullptr);
         TORCH_CHECK(rc == 0, "rn_gemm rejected shape M=", M, " N=", N, " K=", Kp);
         Tensor part = at::empty({(int64_t)(rn_bias_act_grad_splits((int)M, (int)N) + 32) * N}, f32);
         rn_bias_act_grad(c.data_ptr(), nullptr, c.data_ptr(), nullptr, bias_grad->data_ptr(), part.data_ptr<float>(),
-                         (int)M, (int)N, 0, 1, 1, cur_stream());
+                         (int)M, (int)N, c.stride(0), 0, 1, 1, cur_stream());
         return c;
     }
     TORCH_CHECK(rc == 0, "rn_gemm rejected shape M=", M, " N=", N, " K=", Kp);
     if (want_bg) {
+        // as many partial rows as the config that ran wrote: a request (-1, an 11 that falls back) is not one
+        const int ran = gemm_resolve(icfg, split, p).cfg;
         Tensor tmp = at::empty({rn_colsum_ws((int)N)}, f32);
-        rn_colsum_f32(colpart.data_ptr<float>(), (int)rn_gemm_colpart_rows(icfg, (int)M), (int)N, tmp.data_ptr<float>(),
+        rn_colsum_f32(colpart.data_ptr<float>(), (int)rn_gemm_colpart_rows(ran, (int)M), (int)N, tmp.data_ptr<float>(),
                       bias_grad->data_ptr(), 1, cur_stream());
     }
     return c;
@@ -163,7 +166,7 @@ std::tuple<Tensor, Tensor> bias_act_grad(const Tensor& dy, const optional<Tensor
     if (act != 0) { TORCH_CHECK(has(h), "activation grad needs the pre-activation"); CHECK_CONTIG(*h); }
     if (M > 0)
         rn_bias_act_grad(dy.data_ptr(), optr(h), dh.data_ptr(), nullptr, want_bias ? db.data_ptr() : nullptr,
-                         part.data_ptr<float>(), M, N, (int)act, want_bias, accum, cur_stream());
+                         part.data_ptr<float>(), M, N, N, (int)act, want_bias, accum, cur_stream());
     else if (want_bias && !accum) db.zero_();
     return {dh, db};
 }

@@ -95,6 +95,61 @@ inline bool gemm_cfg_takes(int cfg, const GemmProblem& p, int split, bool for_tu
     }
 }
 
+// The native chooser behind cfg / split < 0: a wave-quantisation cost model calibrated on MI355X
+// measurements of these kernels (scripts/microbench.py).  A 128² block runs 2 per CU, a 256² block 1 per
+// CU and ~13 % faster per FLOP (half the L2→LDS bytes per FLOP); a launch takes ceil(tiles / resident
+// slots) rounds.
+struct GemmChoice { int cfg, split; };
+inline GemmChoice gemm_pick(long M, long N, long K, int split_req) {
+    auto ntiles = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
+    const double flop_s_cu = 2.9e12;  // effective per-CU bf16 rate of the 128² config
+    // candidates: cfg id, BM, BN, resident blocks (slots), relative per-CU rate
+    const int cid[4] = {0, 1, 6, 2};
+    const int bm[4] = {128, 256, 256, 256}, bn[4] = {128, 256, 192, 128}, slots[4] = {512, 256, 256, 256};
+    const double rate[4] = {1.0, 1.16, 1.0, 0.9};
+    GemmChoice best = {0, 1};
+    double best_t = 1e30;
+    for (int c = 0; c < 4; ++c) {
+        for (int sp = 1; sp <= 32; sp *= 2) {
+            if (split_req > 0 && sp != split_req) continue;
+            if (split_req <= 0 && sp > 1 && K / sp < 512) break;
+            // split-K only when the unsplit grid cannot fill the resident slots
+            if (split_req <= 0 && sp > 1 && ntiles(bm[c], bn[c]) >= slots[c]) break;
+            const long kps = ((K + sp - 1) / sp + 63) / 64 * 64;
+            const long tiles = ntiles(bm[c], bn[c]) * sp;
+            const long rounds = (tiles + slots[c] - 1) / slots[c];
+            const double per_block = 2.0 * bm[c] * bn[c] * kps / (flop_s_cu * rate[c]) * (c == 0 ? 2.0 : 1.0);
+            double t = rounds * per_block + 2.5e-6;  // + prologue/epilogue per launch
+            if (sp > 1) t += ((double)M * N * (4.0 * sp + 2.0)) / 4.0e12 + 3e-6;
+            if (t < best_t * 0.98) { best_t = t; best = {cid[c], sp}; }
+        }
+    }
+    return best;
+}
+
+// The (cfg, split) that runs for a requested pair: the one place a request is resolved.  rn_gemm launches
+// what this returns, and the binding sizes the column-partial reduction from it (gemm_colpart_rows of the
+// REQUESTED id is wrong whenever the two differ: -1 and an 11 that falls back both run cfg 9, which writes
+// two partial rows per 256-row tile).  cfg 10 has its own launcher and stays; cfg 11 stays where it takes
+// the problem (if its launcher still declines, rn_gemm runs cfg 9: never with column partials, which
+// cfg 11 does not take); an id that is not in the table runs cfg 0's kernel.
+inline GemmChoice gemm_resolve(int cfg, int split, const GemmProblem& p) {
+    if (cfg == 10) return {cfg, split};
+    if (cfg == 11) {
+        if (gemm_cfg_takes(11, p, split)) return {cfg, split};
+        cfg = 9;
+    }
+    if (cfg < 0 || split < 0) {
+        const GemmChoice ch = gemm_pick(p.M, p.N, p.K, split);
+        if (cfg < 0) cfg = gemm_pk_ok(p) ? 9 : ch.cfg;
+        if (split < 0) split = ch.split;
+    }
+    if (cfg == 9 && !gemm_pk_ok(p)) cfg = 1;  // shapes the persistent kernel does not take
+    if (cfg >= 90 && cfg < 90 + 256) return {cfg, split};  // development-only ablation builds of cfg 9
+    if (cfg == 7 || cfg > 11) cfg = 0;  // not a kernel of rn_gemm's
+    return {cfg, split};
+}
+
 // The split-K values the tuner tries, before a config's own limits.  Non-powers of two too: the split that
 // makes tiles × split just fill the 256 CUs (48 tiles × 5 = 240; 36 tiles of 256², GPT-2's 3072×768 weight
 // gradients, × 7 = 252) beats the next power of two by up to 25 %.  Up to 128 slabs only for tiny outputs

@@ -28,9 +28,9 @@ void rn_dropout(const void* x, void* y, long n, float p, uint64_t seed, const ui
 void rn_rng_next(void* state, void* out, hipStream_t st);
 void rn_add(const void* a, const void* b, void* y, long n, int relu, hipStream_t st);
 // part: workspace of >= (rn_bias_act_grad_splits + RN_COLRED_S) * N floats.  db (fp32) / db16 (bf16) written
-// (accum: added into) if want_bias; either may be null.
+// (accum: added into) if want_bias; either may be null.  ld: the row stride of dy, h and dh in elements (>= N).
 void rn_bias_act_grad(const void* dy, const void* h, void* dh, float* db, void* db16, float* part, int M, int N,
-                      int act, int want_bias, int accum, hipStream_t st);
+                      long ld, int act, int want_bias, int accum, hipStream_t st);
 int rn_bias_act_grad_splits(int M, int N);
 // out16[c] (+)= Σ_r in[r][c] for an fp32 [R][C] partial matrix (tmp: rn_colsum_ws(C) floats).
 void rn_colsum_f32(const float* in, int R, int C, float* tmp, void* out16, int accum, hipStream_t st);
@@ -112,7 +112,8 @@ int rn_gemm_sched_init(int dev);
 int* rn_gemm_sched_slot(int dev, hipStream_t st);
 // Workspace floats needed for a split-K launch.
 long rn_gemm_ws_floats(int M, int N, int split);
-// BM of a tile config; rows of the column-partial matrix a config writes (the table in gemm_plan.h)
+// BM of a tile config; rows of the column-partial matrix a config writes (the table in gemm_plan.h).  `cfg` is
+// the config that RAN (gemm_plan.h: gemm_resolve), never a request such as -1.
 int rn_gemm_cfg_bm(int cfg);
 long rn_gemm_colpart_rows(int cfg, int M);
 // C[M,N] = act(alpha · op(A)[M,K] · op(B)[K,N] + bias) + res.

@@ -81,22 +81,23 @@ __global__ void __launch_bounds__(TPB) add_k(const bf16* __restrict__ a, const b
 // dH = dY * act'(H) (written only when ACT != NONE) and partial column sums of dH.
 // Grid: (col_blocks of 512 columns, row_splits).  Each lane owns 8 columns; the
 // block's 4 waves split the rows, partials combine through LDS and land in
-// part[row_split][N] (fp32), summed in fixed order by colsum_finish_k.
+// part[row_split][N] (fp32), summed in fixed order by colsum_finish_k.  dy, h and dh share the
+// row stride ld (elements, >= N); the 16-byte path needs N and ld multiples of 8.
 template <int ACT, bool WANT_BIAS>
 __global__ void __launch_bounds__(TPB) bias_act_grad_k(const bf16* __restrict__ dy, const bf16* __restrict__ h,
                                                        bf16* __restrict__ dh, float* __restrict__ part,
-                                                       int M, int N, int rows_per_split) {
+                                                       int M, int N, long ld, int rows_per_split) {
     __shared__ float red[4][512];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int col = blockIdx.x * 512 + lane * 8;
     const int r0 = blockIdx.y * rows_per_split;
     const int r1 = min(M, r0 + rows_per_split);
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const bool vec = (N % 8 == 0);
+    const bool vec = N % 8 == 0 && ld % 8 == 0 && ((size_t)dy | (size_t)h | (size_t)dh) % 16 == 0;
     if (vec && col < N) {
         for (int r = r0 + wid; r < r1; r += 4) {
             float g[8];
-            long off = (long)r * N + col;
+            long off = (long)r * ld + col;
             load8(dy + off, g);
             if constexpr (ACT != ACT_NONE) {
                 float f[8];
@@ -114,7 +115,7 @@ __global__ void __launch_bounds__(TPB) bias_act_grad_k(const bf16* __restrict__ 
             for (int j = 0; j < 8; ++j) {
                 int c = col + j;
                 if (c < N) {
-                    long off = (long)r * N + c;
+                    long off = (long)r * ld + c;
                     float g = bf2f(dy[off]);
                     if constexpr (ACT != ACT_NONE) {
                         g *= act_grad_f<ACT>(bf2f(h[off]));
@@ -196,13 +197,13 @@ void rn_add(const void* a, const void* b, void* y, long n, int relu, hipStream_t
 }
 
 void rn_bias_act_grad(const void* dy, const void* h, void* dh, float* db, void* db16, float* part, int M, int N,
-                      int act, int want_bias, int accum, hipStream_t st) {
+                      long ld, int act, int want_bias, int accum, hipStream_t st) {
     int cblocks = (N + 511) / 512;
     int splits = 1;
     while (cblocks * splits < 512 && M / (splits * 2) >= 32) splits *= 2;
     int rps = (M + splits - 1) / splits;
     dim3 grid(cblocks, splits);
-#define RN_BAG(A, W) bias_act_grad_k<A, W><<<grid, TPB, 0, st>>>((const bf16*)dy, (const bf16*)h, (bf16*)dh, part, M, N, rps)
+#define RN_BAG(A, W) bias_act_grad_k<A, W><<<grid, TPB, 0, st>>>((const bf16*)dy, (const bf16*)h, (bf16*)dh, part, M, N, ld, rps)
     if (act == ACT_GELU) { if (want_bias) RN_BAG(ACT_GELU, true); else RN_BAG(ACT_GELU, false); }
     else if (act == ACT_RELU) { if (want_bias) RN_BAG(ACT_RELU, true); else RN_BAG(ACT_RELU, false); }
     else { if (want_bias) RN_BAG(ACT_NONE, true); else return; }

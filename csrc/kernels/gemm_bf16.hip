@@ -59,43 +59,6 @@ static_assert(gemm_act_bwd(ACT_RELU_BWD) && gemm_act_bwd(ACT_GELU_BWD) && gemm_a
 static_assert(gemm_act_skinny(ACT_NONE) && gemm_act_skinny(ACT_RELU) && gemm_act_skinny(ACT_GELU) &&
               gemm_act_skinny(ACT_GELU_D) && BK == 64);
 
-namespace {
-
-inline long ntiles(int M, int N, int bm, int bn) { return (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); }
-
-// Tile-config / split-K chooser: a wave-quantisation cost model calibrated on
-// MI355X measurements of this kernel (scripts/microbench.py).  A 128² block runs
-// 2 per CU, a 256² block 1 per CU and ~13 % faster per FLOP (half the L2→LDS
-// bytes per FLOP); a launch takes ceil(tiles / resident slots) rounds.
-struct Choice { int cfg, split; };
-
-inline Choice pick(int M, int N, int K, int split_req) {
-    const double flop_s_cu = 2.9e12;  // effective per-CU bf16 rate of the 128² config
-    // candidates: cfg id, BM, BN, resident blocks (slots), relative per-CU rate
-    const int cid[4] = {0, 1, 6, 2};
-    const int bm[4] = {128, 256, 256, 256}, bn[4] = {128, 256, 192, 128}, slots[4] = {512, 256, 256, 256};
-    const double rate[4] = {1.0, 1.16, 1.0, 0.9};
-    Choice best = {0, 1};
-    double best_t = 1e30;
-    for (int c = 0; c < 4; ++c) {
-        for (int sp = 1; sp <= 32; sp *= 2) {
-            if (split_req > 0 && sp != split_req) continue;
-            if (split_req <= 0 && sp > 1 && K / sp < 512) break;
-            // split-K only when the unsplit grid cannot fill the resident slots
-            if (split_req <= 0 && sp > 1 && ntiles(M, N, bm[c], bn[c]) >= slots[c]) break;
-            const int kps = ((K + sp - 1) / sp + 63) / 64 * 64;
-            const long tiles = ntiles(M, N, bm[c], bn[c]) * sp;
-            const long rounds = (tiles + slots[c] - 1) / slots[c];
-            const double per_block = 2.0 * bm[c] * bn[c] * kps / (flop_s_cu * rate[c]) * (c == 0 ? 2.0 : 1.0);
-            double t = rounds * per_block + 2.5e-6;  // + prologue/epilogue per launch
-            if (sp > 1) t += ((double)M * N * (4.0 * sp + 2.0)) / 4.0e12 + 3e-6;
-            if (t < best_t * 0.98) { best_t = t; best = {cid[c], sp}; }
-        }
-    }
-    return best;
-}
-}  // namespace
-
 extern "C" {
 
 // ---- persistent-GEMM schedule knobs (gemm_pk.h) ----
@@ -205,25 +168,20 @@ int rn_gemm(const void* A, const void* B, void* C, const void* bias, const void*
         return rn_gemm_skinny(A, B, C, bias, res, pre, ws, alpha, M, N, K, lda, ldb, ldc, trans_a, trans_b, act,
                               split, out_f32, accumulate, colpart, st);
     if (!gemm_operands_ok(p)) return -1;
-    if (cfg == 11) {  // one-wave-per-SIMD persistent kernel (gemm_w1.h): x·Wᵀ, plain / bias epilogue
-        if (gemm_cfg_takes(11, p, split)) {
-            GemmArgs w = {};
-            w.A = (const bf16*)A; w.B = (const bf16*)B; w.C = C; w.bias = (const bf16*)bias; w.alpha = alpha;
-            w.res = (const bf16*)res;
-            w.M = M; w.N = N; w.K = K * 2; w.lda = lda * 2; w.ldb = ldb * 2; w.ldc = ldc;
-            if (rn_gemm_launch_w1(w, 0, act, st, !trans_b) == 0) return 0;
-        }
-        cfg = 9;
+    GemmChoice run = gemm_resolve(cfg, split, p);  // what the request becomes (gemm_plan.h)
+    if (run.cfg == 11) {  // one-wave-per-SIMD persistent kernel (gemm_w1.h): x·Wᵀ, plain / bias epilogue
+        GemmArgs w = {};
+        w.A = (const bf16*)A; w.B = (const bf16*)B; w.C = C; w.bias = (const bf16*)bias; w.alpha = alpha;
+        w.res = (const bf16*)res;
+        w.M = M; w.N = N; w.K = K * 2; w.lda = lda * 2; w.ldb = ldb * 2; w.ldc = ldc;
+        if (rn_gemm_launch_w1(w, 0, act, st, !trans_b) == 0) return 0;
+        run = gemm_resolve(9, split, p);  // the launcher declined (cfg 11 takes no column partials: none to size)
     }
+    cfg = run.cfg;
+    split = run.split;
     GemmArgs a = {};
     a.A = (const bf16*)A; a.B = (const bf16*)B; a.C = C; a.bias = (const bf16*)bias; a.res = (const bf16*)res;
     a.pre = (bf16*)pre; a.ws = ws; a.alpha = alpha; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-    if (cfg < 0 || split < 0) {
-        Choice ch = pick(M, N, K, split);
-        if (cfg < 0) cfg = gemm_pk_ok(p) ? 9 : ch.cfg;
-        if (split < 0) split = ch.split;
-    }
-    if (cfg == 9 && !gemm_pk_ok(p)) cfg = 1;  // shapes the persistent kernel does not take
     if (cfg >= 90 && cfg < 90 + 256) {  // timing-only ablation builds of cfg 9 (wrong outputs)
 #ifndef REPLICANN_DEV
         return -1;  // not in a production library (REPLICANN_DEV=1 builds them)

@@ -34,7 +34,7 @@ def bf(*s):
 
 def _pick_split_k(m_out: int, n_out: int, k: int) -> int:
     """A 128²-tile fill model of the weight gradient's split-K, reported beside the measurements
-    (the library's own choice is the native pick() / the autotuner)."""
+    (the library's own choice is the native gemm_pick() / the autotuner)."""
     tiles = math.ceil(m_out / 128) * math.ceil(n_out / 128)
     if tiles >= 512 or k < 1024:
         return 1
