@@ -93,7 +93,9 @@ Tensor gemm(const Tensor& a, const Tensor& b, bool ta, bool tb, const optional<T
     if (!ta && A.stride(0) % 8 != 0) A = A.contiguous();
     if (tb && B.stride(0) % 8 != 0) B = B.contiguous();
     if (has(alpha)) TORCH_CHECK(alpha->scalar_type() == at::kFloat && alpha->is_cuda());
-    const GemmProblem p{M, N, Kp, A.stride(0), B.stride(0), c.stride(0), ta, tb, (int)act, out_fp32, accumulate,
+    // (a one-row operand has no row stride to speak of: a transposed [K][1] made contiguous keeps stride 1)
+    const int64_t lda = A.size(0) == 1 ? A.size(1) : A.stride(0), ldb = B.size(0) == 1 ? B.size(1) : B.stride(0);
+    const GemmProblem p{M, N, Kp, lda, ldb, c.stride(0), ta, tb, (int)act, out_fp32, accumulate,
                         has(bias), has(residual), has(alpha), has(preact), want_bg, (int)split_k};
 
     // one launch of this call's operands: the real one, or a tuning trial into scratch

@@ -32,6 +32,11 @@
 //     the accumulators (no LDS staging, which would need the ring), through buffer stores whose
 //     range check drops out-of-bounds lanes — every wave issues the same number of stores, so
 //     the counted vmcnt waits after an epilogue stay exact;
+//   * which optional operands an epilogue has (bias, residual, accumulate, alpha, store policy,
+//     pre-activation) is a template parameter (EPI, PK_EPI_*): the forms the training step launches
+//     have an instance each and test nothing per tile, the PK_EPI_ANY instance serves the rest
+//     (gemm_pk_launch.h); a tile is addressed by one per-lane offset per column half plus
+//     wave-uniform row steps, the M tail in the descriptor's size (profiles/gemm_seam_r7a.txt);
 //   * bias comes through the scalar cache (s_load, lgkmcnt) so a bias epilogue does not drain
 //     the in-flight operand DMA; epilogues that read a full tile (residual, saved
 //     pre-activation, accumulate target) do wait for it.
@@ -288,7 +293,27 @@ RN_DEV int pk_deq_take(uint32_t v) {
 }
 #pragma clang diagnostic pop
 
-template <bool AK, bool BKC, int ACT, bool SPLIT, bool F32, int DBG = 0, int FP8 = 0, bool DYN = false>
+// Epilogue form of a launch (EPI): which optional epilogue operands the launch has, fixed at compile
+// time so the tile loop tests none of them.  PK_EPI_ANY keeps every choice a run-time one (wave-uniform
+// branches on the argument record): the one instance behind every form that has no instance of its own
+// (pk_launch_layout), and the fp32 / split-K / fp8 / ablation kernels.
+enum : int {
+    PK_EPI_ANY = -1,
+    PK_EPI_BIAS = 1,    // p.bias
+    PK_EPI_RES = 2,     // p.res
+    PK_EPI_ACC = 4,     // p.accumulate (bf16 out: the target is read as an operand tile)
+    PK_EPI_ALPHA = 8,   // p.alpha
+    PK_EPI_NT = 16,     // p.st_nt: non-temporal output stores
+    PK_EPI_PRE = 32,    // p.pre of an activation-forward epilogue (its second output)
+};
+// the form of a bf16-output, unsplit launch
+inline int pk_epi_form(const GemmArgs& a, int act) {
+    return (a.bias ? PK_EPI_BIAS : 0) | (a.res ? PK_EPI_RES : 0) | (a.accumulate ? PK_EPI_ACC : 0) |
+           (a.alpha ? PK_EPI_ALPHA : 0) | (a.st_nt ? PK_EPI_NT : 0) | (act_fwd(act) && a.pre ? PK_EPI_PRE : 0);
+}
+
+template <bool AK, bool BKC, int ACT, bool SPLIT, bool F32, int DBG = 0, int FP8 = 0, bool DYN = false,
+          int EPI = PK_EPI_ANY>
 __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
     // FP8: 0 bf16; 1 e4m3 x e4m3; 2 A e5m2 (a gradient) x B e4m3.  Operand layouts: both K-contiguous
     // (the forward x·Wᵀ), A K- and B MN-contiguous (the data gradient dY·W), both MN-contiguous (the
@@ -345,8 +370,22 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
         return (unsigned)v < (unsigned)(items - rh * grid) ? rh * grid + v : -1;
     };
 
+    // the epilogue form: compile-time constants in a specialised instance
+    constexpr bool ANY = EPI < 0;
+    static_assert(ANY || (!SPLIT && !F32 && !FP8 && DBG == 0), "epilogue forms: bf16 production kernels only");
+    static_assert(ANY || !act_bwd(ACT) || !(EPI & (PK_EPI_BIAS | PK_EPI_RES | PK_EPI_ACC | PK_EPI_PRE)),
+                  "activation backward: its one operand is the saved pre-activation");
+    const bool f_bias = ANY ? p.bias != nullptr : (EPI & PK_EPI_BIAS) != 0;
+    const bool f_res = ANY ? p.res != nullptr : (EPI & PK_EPI_RES) != 0;
+    const bool f_acc = ANY ? p.accumulate != 0 : (EPI & PK_EPI_ACC) != 0;
+    const bool f_alpha = ANY ? p.alpha != nullptr : (EPI & PK_EPI_ALPHA) != 0;
+    const bool f_nt = ANY ? (p.st_nt & 1) != 0 : (EPI & PK_EPI_NT) != 0;
+    const bool f_pre = ANY ? p.pre != nullptr : (EPI & PK_EPI_PRE) != 0;
+    // the bias add is skipped only where x + 0 = x bit for bit: an accumulator that started at +0 is
+    // never -0, but alpha times it can be
+    constexpr bool ADD_BIAS = ANY || (EPI & (PK_EPI_BIAS | PK_EPI_ALPHA)) != 0;
     float alpha = 1.f;
-    if (p.alpha) alpha = *p.alpha;
+    if (f_alpha) alpha = *p.alpha;
     asm volatile("" ::"v"(alpha));  // its load retires here, before any DMA is in flight
 
     // ---- DMA issue stream: half-tile σ = 4·t + h of K-tile t (stream order over the block's
@@ -503,14 +542,32 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
         const long ldc = SPLIT ? (long)p.N : p.ldc;
         constexpr int ES = (SPLIT || F32) ? 4 : 2;
         char* cbase = SPLIT ? (char*)(p.ws + ((long)sid * p.M + m0) * p.N + n0) : (char*)p.C + ((long)m0 * ldc + n0) * ES;
-        const __amdgpu_buffer_rsrc_t crs = pk_rsrc(cbase, 0x7FFFFFF0u);
-        const u32x4 crs_u = pk_rsrc_u(cbase, 0x7FFFFFF0u);
+        // Tile addressing, once per tile.  A lane's byte offset is lane_b2 / lane_bE[nh] (its row lane & 15
+        // and its first column of column half nh; 2^31 when that column is past N, which no row step
+        // brings back into range) plus a wave-uniform row step.  The M tail is the descriptors' size:
+        // the tile's rows below M, so a row at or past M starts at or past the end (a row's columns
+        // end within its ldc elements: N <= ldc).  rlim·ldc·es stays below 2^31 like the offsets.
+        const uint32_t rlim = (uint32_t)min(mlim, BM);
+        auto tile_bytes = [&](int es) -> uint32_t { return rlim * (uint32_t)ldc * (uint32_t)es; };
+        const __amdgpu_buffer_rsrc_t crs = pk_rsrc(cbase, tile_bytes(ES));
+        const u32x4 crs_u = pk_rsrc_u(cbase, tile_bytes(ES));
         // output column of a lane's first value: 8 contiguous columns per lane group G (the permuted B
         // fragments), or for fp8 MN two runs of 4: columns 4G.. (fragment 0) and 16 + 4G.. (fragment 1)
+        constexpr uint32_t OOB = 0x80000000u;
+        const uint32_t row_el = (uint32_t)(lane & 15) * (uint32_t)ldc;
+        // in bytes, for 2-byte elements (operand tiles, bf16 outputs) and for the output's ES
+        uint32_t lane_b2[2], lane_bE[2], lane16_bE[2];
+#pragma unroll
+        for (int nh = 0; nh < 2; ++nh) {
+            const int c = nh * 128 + wc * 32 + (F8B_MN ? 4 : 8) * G;
+            lane_b2[nh] = c < nlim ? (row_el + (uint32_t)c) * 2u : OOB;
+            lane_bE[nh] = c < nlim ? (row_el + (uint32_t)c) * (uint32_t)ES : OOB;
+            lane16_bE[nh] = (F8B_MN && c + 16 < nlim) ? (row_el + (uint32_t)(c + 16)) * (uint32_t)ES : OOB;
+        }
+        const uint32_t wrow_el = (uint32_t)(wr * 64) * (uint32_t)ldc;  // the wave's first row, in elements
         auto off = [&](int mh, int i, int nh, int es, int dc = 0) -> uint32_t {
-            const int r = mh * 128 + wr * 64 + i * 16 + (lane & 15);
-            const int c = nh * 128 + wc * 32 + (F8B_MN ? 4 : 8) * G + dc;
-            return (r < mlim && c < nlim) ? (uint32_t)(((long)r * ldc + c) * es) : 0xFFFFFFF0u;
+            const uint32_t rows = (wrow_el + (uint32_t)(mh * 128 + i * 16) * (uint32_t)ldc) * (uint32_t)es;  // wave-uniform
+            return (dc ? lane16_bE[nh] : (es == ES ? lane_bE[nh] : lane_b2[nh])) + rows;
         };
         // bias: the wave's 2 × 32 columns through the scalar cache, then each lane picks its 8
         float bias[2][8];
@@ -518,7 +575,7 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
         for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
             for (int t = 0; t < 8; ++t) bias[nh][t] = 0.f;
-        if (!SPLIT && !act_bwd(ACT) && p.bias) {  // (activation-backward epilogues never take a bias)
+        if (!SPLIT && !act_bwd(ACT) && f_bias) {  // (activation-backward epilogues never take a bias)
 #pragma unroll
             for (int nh = 0; nh < 2; ++nh) {
                 const int cb = n0 + nh * 128 + wc * 32;
@@ -540,16 +597,18 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
         // full-tile operand read by the epilogue: saved pre-activation (act backward), residual,
         // or the accumulate target (bf16 out)
         const bf16* auxp = SPLIT ? nullptr
-                                 : (act_bwd(ACT) ? p.pre : (p.res ? p.res : ((p.accumulate && !F32) ? (const bf16*)p.C : nullptr)));
+                                 : (act_bwd(ACT) ? p.pre : (f_res ? p.res : ((f_acc && !F32) ? (const bf16*)p.C : nullptr)));
+        // (a specialised activation-backward launch always has its pre-activation: pk_launch_layout)
+        const bool has_aux = SPLIT ? false : (ANY ? auxp != nullptr : (act_bwd(ACT) || (EPI & (PK_EPI_RES | PK_EPI_ACC)) != 0));
         // (loaded one 128-row half at a time: 32 VGPRs, all 8 loads of a half in flight together;
         // both halves at once spill: the kernel is at the 256-VGPR limit)
         // activation-backward epilogues (no bias, no pre-activation store) load BOTH halves up front:
         // one exposed load round trip per tile instead of two
         constexpr bool AUX2 = act_bwd(ACT) && !SPLIT && !F32;
         u32x4 aux[AUX2 ? 2 : 1][4][2];
-        const __amdgpu_buffer_rsrc_t ars = pk_rsrc(auxp ? auxp + (long)m0 * p.ldc + n0 : nullptr, 0x7FFFFFF0u);
-        const u32x4 prs = pk_rsrc_u(act_fwd(ACT) && p.pre ? (void*)(p.pre + (long)m0 * p.ldc + n0) : nullptr,
-                                    act_fwd(ACT) && p.pre ? 0x7FFFFFF0u : 0u);
+        const __amdgpu_buffer_rsrc_t ars = pk_rsrc(has_aux ? auxp + (long)m0 * p.ldc + n0 : nullptr, has_aux ? tile_bytes(2) : 0u);
+        const u32x4 prs = pk_rsrc_u(act_fwd(ACT) && f_pre ? (void*)(p.pre + (long)m0 * p.ldc + n0) : nullptr,
+                                    act_fwd(ACT) && f_pre ? tile_bytes(2) : 0u);
         float csum[2][8];
 #pragma unroll
         for (int nh = 0; nh < 2; ++nh)
@@ -557,7 +616,7 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
             for (int t = 0; t < 8; ++t) csum[nh][t] = 0.f;
 #pragma unroll
         for (int mh = 0; mh < 2; ++mh) {
-            if (auxp && (!AUX2 || mh == 0)) {
+            if (has_aux && (!AUX2 || mh == 0)) {
 #pragma unroll
                 for (int ah = 0; ah < (AUX2 ? 2 : 1); ++ah)
 #pragma unroll
@@ -593,7 +652,7 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
                     }
                     if constexpr (SPLIT) {
                         const uint32_t o = off(mh, i, nh, 4);
-                        const uint32_t o2 = F8B_MN ? off(mh, i, nh, 4, 16) : (o == 0xFFFFFFF0u ? o : o + 16);
+                        const uint32_t o2 = F8B_MN ? off(mh, i, nh, 4, 16) : o + 16;  // (out of range stays so)
                         pk_st16((u32x4){__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
                                     __builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3])},
                             crs_u, o);
@@ -602,8 +661,10 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
                             crs_u, o2);
                         continue;
                     }
+                    if constexpr (ADD_BIAS) {
 #pragma unroll
-                    for (int c = 0; c < 8; ++c) v[c] += bias[nh][c];
+                        for (int c = 0; c < 8; ++c) v[c] += bias[nh][c];
+                    }
                     if constexpr (act_fwd(ACT)) {
                         // pre-activation store (dropped when no pre buffer: zero-size descriptor);
                         // the activation is applied to the bf16-rounded value the backward sees
@@ -619,12 +680,12 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
                             pk_st16(du, prs, off(mh, i, nh, 2));
                         } else {
                             pk_st16(pu, prs, off(mh, i, nh, 2));
-                            if (p.pre) pk_unpack8(pu, v);
+                            if (f_pre) pk_unpack8(pu, v);
 #pragma unroll
                             for (int c = 0; c < 8; ++c) v[c] = act_f<ACT>(v[c]);
                         }
                     }
-                    if (auxp) {
+                    if (has_aux) {
                         float ax[8];
                         pk_unpack8(aux[AUX2 ? mh : 0][i][nh], ax);
                         if constexpr (act_bwd(ACT)) {
@@ -641,9 +702,9 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
                     const uint32_t o = off(mh, i, nh, ES);
                     if constexpr (F32) {
                         float c8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                        if (p.accumulate) {
+                        if (f_acc) {
                             const u32x4 c0 = __builtin_amdgcn_raw_buffer_load_b128(crs, o, 0, 0);
-                            const u32x4 c1 = __builtin_amdgcn_raw_buffer_load_b128(crs, o == 0xFFFFFFF0u ? o : o + 16, 0, 0);
+                            const u32x4 c1 = __builtin_amdgcn_raw_buffer_load_b128(crs, o + 16, 0, 0);
                             const uint32_t w[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
 #pragma unroll
                             for (int d = 0; d < 8; ++d) c8[d] = __builtin_bit_cast(float, w[d]);
@@ -655,9 +716,9 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
                             crs_u, o);
                         pk_st16((u32x4){__builtin_bit_cast(uint32_t, v[4]), __builtin_bit_cast(uint32_t, v[5]),
                                     __builtin_bit_cast(uint32_t, v[6]), __builtin_bit_cast(uint32_t, v[7])},
-                            crs_u, o == 0xFFFFFFF0u ? o : o + 16);
+                            crs_u, o + 16);
                     } else {
-                        if (p.res && p.accumulate) {  // both: residual above, accumulate target here
+                        if (f_res && f_acc) {  // both: residual above, accumulate target here
                             float c8[8];
                             pk_unpack8(__builtin_amdgcn_raw_buffer_load_b128(crs, o, 0, 0), c8);
 #pragma unroll
@@ -669,7 +730,7 @@ __global__ void __launch_bounds__(512, 1) gemm_pk(GemmArgs p) {
                         else if constexpr (F8B_MN) {  // columns 4G.. and 16 + 4G..
                             pk_st8((u32x2v){ou.x, ou.y}, crs_u, o);
                             pk_st8((u32x2v){ou.z, ou.w}, crs_u, off(mh, i, nh, 2, 16));
-                        } else if (p.st_nt & 1) pk_st16_nt(ou, crs_u, o);          // wave-uniform choice
+                        } else if (f_nt) pk_st16_nt(ou, crs_u, o);          // wave-uniform choice
                         else pk_st16(ou, crs_u, (DBG & 32) ? 0xFFFFFFF0u : o);   // ablation: no traffic
                     }
                 }
@@ -941,9 +1002,10 @@ inline int* pk_sched_slot(const GemmArgs& a, hipStream_t st) {
     return rn_gemm_sched_slot(dev, st);
 }
 
-template <bool AK, bool BKC, int ACT, bool SPLIT, bool F32, int DBG = 0, int FP8 = 0, bool DYN = false>
+template <bool AK, bool BKC, int ACT, bool SPLIT, bool F32, int DBG = 0, int FP8 = 0, bool DYN = false,
+          int EPI = PK_EPI_ANY>
 void launch_pk_t(GemmArgs& a, hipStream_t st) {
-    auto kern = gemm_pk<AK, BKC, ACT, SPLIT, F32, DBG, FP8, DYN>;
+    auto kern = gemm_pk<AK, BKC, ACT, SPLIT, F32, DBG, FP8, DYN, EPI>;
     static int attr_dev = -1;  // the >64 KiB LDS opt-in, per device the process launches on
     int dev = 0;
     (void)hipGetDevice(&dev);

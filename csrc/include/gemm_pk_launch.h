@@ -9,6 +9,21 @@
 namespace rn_gemm_detail {
 
 
+// Launches the instance specialised for `form` (gemm_pk.h, PK_EPI_*) if FORMS lists it.
+template <bool AK, bool BKC, bool DYN, int ACT, int... FORMS>
+bool pk_launch_form(GemmArgs& a, int form, hipStream_t st) {
+    bool hit = false;
+    ((form == FORMS ? (launch_pk_t<AK, BKC, ACT, false, false, 0, 0, DYN, FORMS>(a, st), hit = true) : false), ...);
+    return hit;
+}
+
+// The epilogue forms with an instance of their own are the ones the models' training step launches
+// (ops/linear.py, ops/loss.py; the tuner times the same launches):
+//   x·Wᵀ (forward):  plain, plain with non-temporal stores (the LM head's logits), bias (qkv),
+//                    bias + residual (attention projection, fc2), saved-derivative GELU with bias (fc1);
+//   dY·W (dgrad):    plain, alpha (the LM head's hidden-state gradient), the multiply by the saved
+//                    GELU derivative (fc2's dgrad).
+// Every other form runs the PK_EPI_ANY instance of the same kernel below.
 template <bool AK, bool BKC, bool DYN>
 void pk_launch_layout(GemmArgs& a, int act, hipStream_t st) {
     constexpr bool dgrad = AK && !BKC;  // activation-backward epilogues: dY·W layout only
@@ -20,6 +35,18 @@ void pk_launch_layout(GemmArgs& a, int act, hipStream_t st) {
     if (a.out_f32) {
         launch_pk_t<AK, BKC, ACT_NONE, false, true, 0, false, DYN>(a, st);
         return;
+    }
+    a.st_nt = rn_gemm_st_nt(a);
+    const int form = pk_epi_form(a, act);
+    if constexpr (fwd) {
+        if (act == ACT_NONE && pk_launch_form<AK, BKC, DYN, ACT_NONE, 0, PK_EPI_NT, PK_EPI_BIAS, PK_EPI_BIAS | PK_EPI_RES>(a, form, st))
+            return;
+        if (act == ACT_GELU_D && pk_launch_form<AK, BKC, DYN, ACT_GELU_D, PK_EPI_BIAS | PK_EPI_PRE>(a, form, st)) return;
+    }
+    if constexpr (dgrad) {
+        if (act == ACT_NONE && pk_launch_form<AK, BKC, DYN, ACT_NONE, 0, PK_EPI_ALPHA>(a, form, st)) return;
+        // (the saved-derivative multiply; a specialised ACT_GELU_BWD needs more than 256 VGPRs and spills)
+        if (act == ACT_MUL_BWD && a.pre && pk_launch_form<AK, BKC, DYN, ACT_MUL_BWD, 0>(a, form, st)) return;
     }
     switch (act) {
         case ACT_GELU: launch_pk_t<AK, BKC, ACT_GELU, false, false, 0, false, DYN>(a, st); return;
