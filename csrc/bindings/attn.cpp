@@ -1,6 +1,6 @@
 // Attention and decoding bindings: attn_fwd and the backward forms, attn_decode, attn_window, linear_kv,
-// sample_logits (kernels: attention*.hip, attention_decode.hip, attention_window.hip, gemm_skinny.hip,
-// sampling.hip).  Not named attention.cpp:
+// sample_logits, replicann_spec::verify (kernels: attention*.hip, attention_decode.hip, attention_window.hip,
+// gemm_skinny.hip, sampling.hip, spec_verify.hip).  Not named attention.cpp:
 // the build keys its per-unit compiler flags by file stem, and those of attention.hip are for device code.
 #include "binding_util.h"
 #include "rn_api.h"
@@ -172,6 +172,80 @@ std::tuple<Tensor, Tensor> sample_logits(const Tensor& logits, double temperatur
     return {tokens, kept};
 }
 
+// speculative sampling, verification (spec_verify.hip): target (B, K+1, V) and draft (B, K, V) logits of
+// one dtype (bf16 / fp32) with a unit last stride and row strides >= V, drafts (B, K) int64 ->
+// (tokens (B, K+1) int64, matched (B,) int64).  u: (B, K+1, 2) fp32 or seed_buf; params as for
+// sample_logits.  check_drafts reads the drafts' range on the host (a sync: not inside a capture);
+// without it a draft outside [0, V) is rejected on the device.
+std::tuple<Tensor, Tensor> spec_verify(const Tensor& target, const Tensor& draft, const Tensor& drafts,
+                                       double temperature, int64_t top_k, double top_p, const optional<Tensor>& u,
+                                       const optional<Tensor>& seed_buf, const optional<Tensor>& params,
+                                       bool check_drafts) {
+    CHECK_CUDA(target); CHECK_CUDA(draft); CHECK_CUDA(drafts); GUARD(target);
+    TORCH_CHECK(target.scalar_type() == at::kBFloat16 || target.scalar_type() == at::kFloat,
+                "speculative_verify: logits must be bfloat16 or float32, got ", target.scalar_type());
+    TORCH_CHECK(draft.scalar_type() == target.scalar_type(), "speculative_verify: target and draft logits differ in dtype: ",
+                target.scalar_type(), " and ", draft.scalar_type());
+    TORCH_CHECK(draft.device() == target.device() && drafts.device() == target.device(),
+                "speculative_verify: target_logits, draft_logits and drafts must be on one device");
+    TORCH_CHECK(target.dim() == 3 && draft.dim() == 3 && drafts.dim() == 2,
+                "speculative_verify: need target (B, K+1, V), draft (B, K, V) and drafts (B, K), got ", target.sizes(),
+                ", ", draft.sizes(), ", ", drafts.sizes());
+    const int64_t B = target.size(0), K = target.size(1) - 1, V = target.size(2);
+    TORCH_CHECK(K >= 1 && K <= 15, "speculative_verify: K must be in 1..15, got ", K);
+    TORCH_CHECK(V >= 1 && V <= (1 << 30), "speculative_verify: V must be in 1..2^30, got ", V);
+    TORCH_CHECK(B * (K + 1) <= (1 << 30), "speculative_verify: B · (K + 1) = ", B * (K + 1), " exceeds 2^30");
+    TORCH_CHECK(draft.size(0) == B && draft.size(1) == K && draft.size(2) == V && drafts.size(0) == B &&
+                    drafts.size(1) == K,
+                "speculative_verify: need target (B, K+1, V), draft (B, K, V) and drafts (B, K), got ", target.sizes(),
+                ", ", draft.sizes(), ", ", drafts.sizes());
+    TORCH_CHECK(drafts.scalar_type() == at::kLong && drafts.is_contiguous(),
+                "speculative_verify: drafts must be a contiguous int64 tensor");
+    for (const Tensor* t : {&target, &draft})
+        TORCH_CHECK(t->stride(2) == 1 && t->stride(1) >= V && (B == 1 || t->stride(0) >= t->size(1) * t->stride(1)),
+                    "speculative_verify: logits need a unit last stride and non-overlapping rows of stride >= V, got strides ",
+                    t->strides());
+    TORCH_CHECK(temperature >= 0.0 && temperature < INFINITY,
+                "speculative_verify: temperature must be finite and >= 0, got ", temperature);
+    TORCH_CHECK(top_k >= 0, "speculative_verify: top_k must be >= 0 (0 = off), got ", top_k);
+    TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "speculative_verify: top_p must be in (0, 1], got ", top_p);
+    const bool has_u = has(u), has_seed = has(seed_buf);
+    TORCH_CHECK(has_u != has_seed, "speculative_verify: exactly one of u and seed_buf must be given");
+    if (has_u)
+        TORCH_CHECK(u->scalar_type() == at::kFloat && u->dim() == 3 && u->size(0) == B && u->size(1) == K + 1 &&
+                        u->size(2) == 2 && u->is_contiguous() && u->device() == target.device(),
+                    "speculative_verify: u must be a contiguous (B, K+1, 2) float32 tensor on the logits' device");
+    const uint64_t* seed = seed_ptr(seed_buf);
+    if (has_seed)
+        TORCH_CHECK(seed_buf->device() == target.device(), "speculative_verify: seed_buf must be on the logits' device");
+    const bool has_params = has(params);
+    if (has_params)
+        TORCH_CHECK(params->scalar_type() == at::kFloat && params->numel() == 3 && params->is_contiguous() &&
+                        params->device() == target.device(),
+                    "speculative_verify: params must be 3 contiguous float32 values (temperature, top_k, top_p) on "
+                    "the logits' device");
+    Tensor tokens = at::empty({B, K + 1}, target.options().dtype(at::kLong));
+    Tensor matched = at::empty({B}, target.options().dtype(at::kLong));
+    if (B == 0) return {tokens, matched};
+    if (check_drafts) {
+        const auto [lo, hi] = at::aminmax(drafts);
+        TORCH_CHECK(lo.item<int64_t>() >= 0 && hi.item<int64_t>() < V, "speculative_verify: drafts must lie in [0, ", V,
+                    "), got ", lo.item<int64_t>(), " .. ", hi.item<int64_t>());
+    }
+    Tensor cand = at::empty({B, K + 1}, target.options().dtype(at::kInt));
+    const long tld[2] = {(long)target.stride(0), (long)target.stride(1)};
+    const long dld[2] = {(long)draft.stride(0), (long)draft.stride(1)};
+    const int rc = rn_spec_verify(target.data_ptr(), tld, draft.data_ptr(), dld, drafts.data_ptr<int64_t>(),
+                                  target.scalar_type() == at::kBFloat16, (int)B, (int)K, (int)V, (float)temperature,
+                                  (int)std::min<int64_t>(top_k, 1 << 30), (float)top_p,
+                                  has_params ? params->data_ptr<float>() : nullptr,
+                                  has_u ? u->data_ptr<float>() : nullptr, seed,
+                                  reinterpret_cast<uint32_t*>(cand.data_ptr<int>()), tokens.data_ptr<int64_t>(),
+                                  matched.data_ptr<int64_t>(), cur_stream());
+    TORCH_CHECK(rc == 0, "speculative_verify: unsupported arguments (B=", B, ", K=", K, ", V=", V, ")");
+    return {tokens, matched};
+}
+
 std::tuple<Tensor, Tensor> attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& bias,
                                     double scale, bool causal, double p, int64_t seed,
                                     const optional<Tensor>& seed_buf) {
@@ -289,6 +363,16 @@ TORCH_LIBRARY_FRAGMENT(replicann_decode, m) {
 
 TORCH_LIBRARY_IMPL(replicann_decode, CUDA, m) {
     m.impl("attn_window", &attn_window);
+}
+
+// speculative sampling: a namespace of its own too (the replicann_decode:: list is frozen as well)
+TORCH_LIBRARY_FRAGMENT(replicann_spec, m) {
+    m.def("verify(Tensor target_logits, Tensor draft_logits, Tensor drafts, float temperature, int top_k, float top_p, "
+          "Tensor? u, Tensor? seed_buf, Tensor? params, bool check_drafts) -> (Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(replicann_spec, CUDA, m) {
+    m.impl("verify", &spec_verify);
 }
 
 TORCH_LIBRARY_IMPL(replicann, CUDA, m) {

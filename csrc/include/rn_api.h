@@ -231,6 +231,18 @@ int rn_sample_logits(const void* logits, int is_bf16, long ld, int B, int V, flo
                      float top_p, const float* params, const float* u, const uint64_t* seed,
                      int64_t* tokens, int* kept, hipStream_t st);
 
+// ------------------------------------------------------------------ spec_verify.hip
+// Speculative sampling, verification: target (B, K+1, V) / draft (B, K, V) logits, both bf16 or both
+// fp32, with the element strides tld / dld (batch, position; the position stride >= V, the last one
+// 1), drafts (B, K) int64 contiguous (a value outside [0, V) is rejected on the device), 1 <= K <= 15.
+// u: (B, K+1, 2) fp32 (acceptance draw, resample / bonus draw) or seed (position w = b·(K+1)+i draws
+// hash_uniform(*seed, 2w) and (.., 2w + 1)): exactly one; params as for rn_sample_logits.
+// cand: B·(K+1) uint32 of workspace; tokens (B, K+1) and matched (B) int64.
+int rn_spec_verify(const void* target, const long* tld, const void* draft, const long* dld,
+                   const int64_t* drafts, int is_bf16, int B, int K, int V, float temperature, int top_k,
+                   float top_p, const float* params, const float* u, const uint64_t* seed, uint32_t* cand,
+                   int64_t* tokens, int64_t* matched, hipStream_t st);
+
 // ------------------------------------------------------------------ fp8.hip
 // state: 4 floats per tensor [scale, amax, amax the scale came from, -]
 // state is (re)initialised here (memset node + 2 kernels): current scaling.

@@ -5,6 +5,7 @@
     replicann eval  --model gpt2-small --checkpoint ck.pt
     replicann generate --model gpt2-small --checkpoint ck.pt --prompt 464,2068 --new 32 --top-k 50
     replicann generate --model gpt2-medium --draft-model gpt2-small --draft-k 4 --temperature 0
+    replicann generate --model gpt2-medium --draft-model gpt2-small --temperature 0.8 --top-k 50 --sampler native
     replicann build            # compile the gfx950 extension in-tree (hipcc --offload-arch=gfx950)
     replicann <train args...>  # no command: train (kept for ``python -m replicann --model ...``)
 

@@ -3,8 +3,9 @@
 ``KVCache`` owns everything that depends on its mode; ``generate`` is the sampling loop (uniform or
 ragged) over one ``_StepDriver``, which resolves the cache and runs the one-token step eagerly or as
 a hipGraph kept in the model's ``_GraphRegistry``.  The model (``models/gpt2.py``) keeps the pass.
-With a draft model, ``generate`` is greedy speculative decoding (``_speculative_loop``): the draft's
-one-token steps, the target's window step (``_WindowDriver``, ``capture_window``) and ``accept``.
+With a draft model, ``generate`` is speculative decoding (``_speculative_loop``): the draft's one-token
+steps, the target's window step (``_WindowDriver``, ``capture_window``) and ``accept`` — greedy, or with
+``sampler="native"`` speculative sampling (``ops.speculative_verify`` decides what ``accept`` commits).
 """
 
 from __future__ import annotations
@@ -245,12 +246,13 @@ class _GraphRegistry(dict):
     """One model's captured decode steps kept across ``generate`` calls, least recently used first:
     (batch, cache length, dtype, device, parameter storage[, "ragged" for the per-sequence step]
     [, "sampler" for a step captured together with the native sampler][, "window", T for the window step of
-    T tokens per row: its output is the greedy ids (B, T)]) → (cache, graph, token buffer, logits), so a serving loop captures once per (batch, length bucket).  A sampler entry holds the
+    T tokens per row: its output is the greedy ids (B, T)][, "logits" for the window step whose output is the
+    logits (B, T, vocab) instead]) → (cache, graph, token buffer, logits), so a serving loop captures once per (batch, length bucket).  A sampler entry holds the
     sampled tokens (B, 1) in place of the logits, then the device tensor its settings are read from:
     one graph whatever the temperature / top_k / top_p.
     At most DECODE_GRAPHS_MAX (REPLICANN_DECODE_GRAPHS, default 4) are kept; each holds its KV cache."""
 
-    def lookup(self, model, B, L, ragged, use, sampler=False, window=None):
+    def lookup(self, model, B, L, ragged, use, sampler=False, window=None, logits=False):
         """(key, its stored entry — now the most recently used — or None).  The parameters' storage
         is part of the key: a graph reads them by address, so entries captured before a parameter was
         re-assigned (p.data = ...) are dropped here, whether or not this call will ``use`` a graph."""
@@ -258,6 +260,7 @@ class _GraphRegistry(dict):
         key = (B, L, model.wte.dtype, model.wte.device, sig) + (("ragged",) if ragged else ())
         key += ("sampler",) if sampler else ()
         key += ("window", window) if window else ()  # the captured window step of this many tokens per row
+        key += ("logits",) if logits else ()  # ... returning its logits, not the greedy ids
         for k in [k for k in self if k[4] != sig]:
             del self[k]
         entry = self.pop(key, None) if use else None
@@ -325,30 +328,32 @@ def capture_step(model, cache, B, sampler=None):
     return (graph, tok, out) if sampler is None else (graph, tok, out, params)
 
 
-def capture_window(model, cache, B, T):
+def capture_window(model, cache, B, T, logits=False):
     """Record the window step ``model.decode_window`` of ``T`` tokens per row as a hipGraph, the way
     ``capture_step`` does (one eager warm-up on a side stream; ``cache`` — in per-sequence mode — is
     put back after both runs, so the positions after the capture equal the positions before it; the
     rows the runs wrote are past them: not valid).  Returns (graph, tok (B, T), ids (B, T)): the caller
-    writes the window's tokens into ``tok``, replays and reads the greedy ids."""
+    writes the window's tokens into ``tok``, replays and reads the greedy ids — with ``logits`` the step is
+    ``model.decode_window_logits`` and the static output its logits (B, T, vocab)."""
+    step = model.decode_window_logits if logits else model.decode_window
     dev = model.wte.device
     tok = torch.zeros(B, T, dtype=torch.long, device=dev)
     snap = cache.snapshot()
     side = torch.cuda.Stream(dev)
     side.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(side):
-        model.decode_window(tok, cache)
+        step(tok, cache)
     torch.cuda.current_stream(dev).wait_stream(side)
     cache.restore(snap)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        out = model.decode_window(tok, cache)
+        out = step(tok, cache)
     cache.restore(snap)
     return graph, tok, out
 
 
-def accept(drafts, greedy, *, budget=None, finished=None, eos=None, pad=0):
-    """What one round of greedy speculative decoding commits — a pure tensor function, no host value.
+def accept(drafts, greedy, *, matched=None, budget=None, finished=None, eos=None, pad=0):
+    """What one round of speculative decoding commits — a pure tensor function, no host value.
 
     ``drafts`` (B, K): the draft model's tokens d_1 .. d_K after the pending token; ``greedy``
     (B, K+1): the target's greedy token after each window position [pending, d_1 .. d_K].  With ``a``
@@ -357,11 +362,16 @@ def accept(drafts, greedy, *, budget=None, finished=None, eos=None, pad=0):
     the first ``eos`` (kept) and at the row's ``budget`` (B,), the tokens it may still emit; a
     ``finished`` (B,) row commits nothing.
 
+    Speculative sampling passes what ``ops.speculative_verify`` returned: ``greedy`` is then its tokens (B, K+1)
+    — the accepted drafts and the resampled / bonus token — and ``matched`` (B,) its accepted length a, which
+    the verifier decided; the cuts are the same.
+
     Returns (count (B,), tokens (B, K+1), matched (B,)): how many tokens each row commits, the tokens
     themselves (``pad`` past count) and the agreed length a before any cut."""
     B, K = drafts.shape
     j = torch.arange(K + 1, device=drafts.device).view(1, K + 1)
-    matched = (drafts == greedy[:, :K]).long().cumprod(1).sum(1)
+    if matched is None:
+        matched = (drafts == greedy[:, :K]).long().cumprod(1).sum(1)
     count = matched + 1
     if eos is not None:  # the first EOS among the committed tokens ends them
         first = torch.where(greedy == eos, j, K + 1).amin(1)
@@ -373,10 +383,10 @@ def accept(drafts, greedy, *, budget=None, finished=None, eos=None, pad=0):
     return count, torch.where(j < count.view(B, 1), greedy, torch.full_like(greedy, pad)), matched
 
 
-def _check_draft(model, draft, draft_k, temperature, need):
-    if temperature != 0:
-        raise ValueError("generate(draft=...) is greedy: temperature must be 0 (sampling with a draft model needs "
-                         "rejection sampling and is not supported)")
+def _check_draft(model, draft, draft_k, temperature, need, native):
+    if temperature != 0 and not native:
+        raise ValueError("generate(draft=...) with sampler='torch' is greedy: temperature must be 0 (speculative "
+                         "sampling, temperature > 0 with a draft model, needs sampler='native')")
     if not isinstance(draft_k, int) or not 1 <= draft_k <= 15:
         raise ValueError(f"draft_k must be in 1..15, got {draft_k}")
     for what, a, b in (("vocab_size", model.config.vocab_size, draft.config.vocab_size),
@@ -392,35 +402,52 @@ def _check_draft(model, draft, draft_k, temperature, need):
 
 class _WindowDriver:
     """One speculative ``generate`` call's target side: the cache and the window step of T tokens per
-    row, eager or as a hipGraph kept in the model's registry under (..., "ragged", "window", T)."""
+    row, eager or as a hipGraph kept in the model's registry under (..., "ragged", "window", T).  ``logits``: the
+    step returns the window's logits (B, T, vocab), not the greedy ids (its own registry key)."""
 
-    def __init__(self, model, B, length, T, graph):
+    def __init__(self, model, B, length, T, graph, logits=False):
         length = min(model.config.block_size, -(-length // DECODE_LEN_BUCKET) * DECODE_LEN_BUCKET)
         self.model, self.B, self.T, self.graph, self.graphs = model, B, T, graph, registry(model)
-        self.key, self.entry = self.graphs.lookup(model, B, length, True, graph, window=T)
+        self.logits = logits
+        self.key, self.entry = self.graphs.lookup(model, B, length, True, graph, window=T, logits=logits)
         self.cache = KVCache(model.config.n_layer, length) if self.entry is None else self.entry[0]
         self.cache.reset()
 
     def step(self, toks):
-        """Greedy ids (B, T) after every position of the window ``toks`` (B, T); a replay returns its static buffer."""
+        """Greedy ids (B, T) — or logits (B, T, vocab) — after every position of the window ``toks`` (B, T); a
+        replay returns its static buffer."""
         if not self.graph:
-            return self.model.decode_window(toks, self.cache)
+            return (self.model.decode_window_logits if self.logits else self.model.decode_window)(toks, self.cache)
         if self.entry is None:
             self.graphs.make_room()  # before the capture allocates
-            self.entry = self.graphs[self.key] = (self.cache, *capture_window(self.model, self.cache, self.B, self.T))
+            self.entry = self.graphs[self.key] = (self.cache, *capture_window(self.model, self.cache, self.B, self.T,
+                                                                              self.logits))
         _, graph, buf, out = self.entry
         buf.copy_(toks)
         graph.replay()
         return out
 
 
-def _speculative_loop(model, draft, idx, plens, max_new_tokens, K, eos, pad, use_graph, ragged, stats):
-    """Greedy generation of ``model`` with ``draft`` proposing K tokens a round (see ``generate``)."""
+def _speculative_loop(model, draft, idx, plens, max_new_tokens, K, eos, pad, use_graph, ragged, stats, sampling=None):
+    """Generation of ``model`` with ``draft`` proposing K tokens a round (see ``generate``): greedy, or with
+    ``sampling`` = (temperature, top_k, top_p, generator) speculative sampling on the native sampler."""
     (B, Tm), dev = idx.shape, idx.device  # idx: the prompts cut to the longest one
+    V = model.config.vocab_size
+
+    def pick(logits):
+        """(B, V) logits → (B,) ids: the argmax, or ``ops.sample_logits`` under the call's settings (a device
+        seed on a GPU model, the host generator's uniforms on a CPU model)."""
+        if sampling is None:
+            return logits.argmax(-1)
+        t, k, p, gen = sampling
+        if logits.is_cuda:
+            return ops.sample_logits(logits, t, k, p, seed_buf=rng.next_seed(dev))[0][:, 0]
+        return ops.sample_logits(logits.float(), t, k, p, u=torch.rand(B, generator=gen))[0][:, 0]
+
     if pad is None:
         pad = eos if eos is not None else 0
     need = Tm + max_new_tokens + K
-    target = _WindowDriver(model, B, need, K + 1, use_graph)
+    target = _WindowDriver(model, B, need, K + 1, use_graph, logits=sampling is not None)
     drafter = _StepDriver(draft, B, need, True, use_graph, (0, None, None, None), False)
     lens = torch.tensor(plens, dtype=torch.long, device=dev)  # each row's length so far
     # rows prompt ‖ generated, pad elsewhere (K + 1 spare columns: a round's padded tail lands in range)
@@ -430,7 +457,7 @@ def _speculative_loop(model, draft, idx, plens, max_new_tokens, K, eos, pad, use
     j = torch.arange(K + 1, device=dev).view(1, K + 1)
     # both models prefill the prompts; the target's first token is committed at once and is "pending": the
     # last committed token, not yet in either cache (it goes to row cache.pos_t of both)
-    pending = model.decode_step(idx, target.cache, lens=plens).argmax(-1)
+    pending = pick(model.decode_step(idx, target.cache, lens=plens))
     draft.decode_step(idx, drafter.cache, lens=plens)
     tokens.scatter_(1, lens.view(B, 1), pending.view(B, 1))
     lens += 1
@@ -441,6 +468,12 @@ def _speculative_loop(model, draft, idx, plens, max_new_tokens, K, eos, pad, use
     drafted, accepted = torch.zeros_like(lens), torch.zeros_like(lens)
     rounds_run = torch.zeros((), dtype=torch.long, device=dev)
     drafts = torch.empty(B, K, dtype=torch.long, device=dev)
+    if sampling is not None:
+        # the rows the drafts are drawn from: a replayed step's static logits are overwritten by the next replay.
+        # Rows padded to 16 bytes, like the target's (a slice of the padded LM head): the verifier reads both in
+        # one slot mapping with vector loads
+        dlogits = torch.empty(B, K, -(-V // 8) * 8, dtype=torch.float32 if not model.wte.is_cuda else model.wte.dtype,
+                              device=dev)[..., :V]
     # an unfinished row commits 1 .. K + 1 tokens a round: no row can be done before `least` rounds without an
     # EOS, and every row is after `most`; in between the device is asked every DECODE_EOS_CHECK rounds
     most, least = max_new_tokens - 1, -(-(max_new_tokens - 1) // (K + 1))
@@ -456,11 +489,23 @@ def _speculative_loop(model, draft, idx, plens, max_new_tokens, K, eos, pad, use
         tok = pending.view(B, 1)
         # K + 1 draft steps: the last one only writes d_K's cache row (needed when every draft is accepted)
         for i in range(K + 1):
-            tok = drafter.step(tok).argmax(-1, keepdim=True)
+            logits = drafter.step(tok)
             if i < K:
+                tok = pick(logits).view(B, 1)
                 drafts[:, i] = tok[:, 0]
+                if sampling is not None:
+                    dlogits[:, i].copy_(logits)
         greedy = target.step(torch.cat([pending.view(B, 1), drafts], 1))
-        count, out, matched = accept(drafts, greedy, budget=budget, finished=finished, eos=eos, pad=pad)
+        matched = None
+        if sampling is not None:  # `greedy` holds the window's logits: the verifier's tokens take its place
+            t, k, p, gen = sampling
+            if greedy.is_cuda:  # two launches after the window step (or its replay); no host value
+                greedy, matched = ops.speculative_verify(greedy, dlogits, drafts, t, k, p, seed_buf=rng.next_seed(dev),
+                                                         check_drafts=False)
+            else:
+                greedy, matched = ops.speculative_verify(greedy.float(), dlogits, drafts, t, k, p,
+                                                         u=torch.rand(B, K + 1, 2, generator=gen))
+        count, out, matched = accept(drafts, greedy, matched=matched, budget=budget, finished=finished, eos=eos, pad=pad)
         tokens.scatter_(1, lens.view(B, 1) + j, out)  # pad past count: those columns are not committed yet
         pending = torch.where(count > 0, out.gather(1, (count - 1).clamp(min=0).view(B, 1))[:, 0], pending)
         lens += count
@@ -558,8 +603,8 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     DECODE_EOS_CHECK steps).  Returns ``(tokens, lens)``: tokens (B, max(lens)), rows
     ``prompt_b ‖ generated_b`` right-padded with the pad id, and lens (B,) each row's total length.
 
-    Speculative decoding (``draft``: a smaller model of the same vocabulary, device and dtype; greedy only,
-    ``temperature=0``): the output is this model's greedy generation, token for token up to near-ties of
+    Speculative decoding (``draft``: a smaller model of the same vocabulary, device and dtype).  With
+    ``temperature=0`` the output is this model's greedy generation, token for token up to near-ties of
     the arithmetic, produced in rounds.  Both models prefill the prompts; a round replays the draft's
     one-token step ``draft_k`` + 1 times from the last committed token (the extra step writes the last
     draft's cache row; its output is dropped), runs this model's window step over the committed token
@@ -567,7 +612,15 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     ``accept`` keeps — the agreed drafts plus one token of this model's own, cut at an EOS and at
     ``max_new_tokens`` — and moves both caches to the committed position, all on the device.  The
     return types are the same; ``stats`` (a dict) receives ``rounds`` and, per row, ``drafted`` and
-    ``accepted`` (draft tokens proposed / agreed with).  The caches hold ``draft_k`` rows more than the
+    ``accepted`` (draft tokens proposed / agreed with).  With ``temperature > 0`` it is speculative sampling
+    and needs ``sampler="native"`` (the default sampler raises): the first token and every draft token are drawn
+    with ``ops.sample_logits`` under the call's ``temperature`` / ``top_k`` / ``top_p``, the draft logits of a
+    round are kept, the window step returns this model's logits (``decode_window_logits``) and
+    ``ops.speculative_verify`` accepts each draft with probability min(1, p/q) and draws the token after the
+    last accepted one from the residual max(p - q, 0) (after ``draft_k`` accepted drafts: a bonus token from
+    p), so every committed token is distributed as this model's own sampling; ``accept`` applies the same
+    cuts.  The verifier's two launches are issued after the window step (with ``graph``: after its replay, not
+    captured with it); the randomness is that of ``sampler="native"``.  The caches hold ``draft_k`` rows more than the
     tokens: prompt + ``max_new_tokens`` + ``draft_k`` must fit both models' block_size."""
     B, T0 = idx.shape
     ragged = prompt_lens is not None or eos_token_id is not None
@@ -591,13 +644,14 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     if draft is not None:
         if max_new_tokens < 1:
             raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
-        _check_draft(model, draft, draft_k, temperature, Tm + max_new_tokens)
+        _check_draft(model, draft, draft_k, temperature, Tm + max_new_tokens, native)
         modes = [(m, m.training) for m in (model, draft)]
         try:
             for m, _ in modes:
                 m.eval()
             return _speculative_loop(model, draft, idx[:, :Tm], plens, max_new_tokens, draft_k, eos_token_id,
-                                     pad_token_id, use_graph, ragged, stats)
+                                     pad_token_id, use_graph, ragged, stats,
+                                     (temperature, top_k, top_p, generator) if temperature != 0 else None)
         finally:
             for m, was in modes:
                 m.train(was)

@@ -213,6 +213,13 @@ class GPT2(nn.Module):
         (``decoding.capture_window``)."""
         return self._window_logits(idx, cache).argmax(-1)
 
+    @torch.no_grad()
+    def decode_window_logits(self, idx, cache):
+        """``decode_window`` returning the window's logits (B, T, vocab) instead of the greedy ids: what
+        speculative sampling verifies the drafts against (``ops.speculative_verify``).  The cache is
+        treated the same way."""
+        return self._window_logits(idx, cache)
+
     def _device_position_step(self, tok, cache):
         """The one-token step ``tok`` (B, 1) → (B, vocab) logits that ``generate`` runs or captures."""
         return self.decode_step(tok, cache)

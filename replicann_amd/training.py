@@ -515,7 +515,7 @@ def generate_main(argv=None):
     ap.add_argument("--model-kwargs", type=json.loads, default={})
     ap.add_argument("--draft-model", default=None,
                     help="speculative decoding: a smaller GPT-2 model that proposes --draft-k tokens a round "
-                         "(greedy only: --temperature 0)")
+                         "(--temperature 0: greedy; a temperature > 0 is speculative sampling and needs --sampler native)")
     ap.add_argument("--draft-checkpoint", default=None)
     ap.add_argument("--draft-k", type=int, default=4)
     a = ap.parse_args(argv)

@@ -34,6 +34,11 @@ yields cost one by one), and ``generate`` end to end with and without the draft 
 weights, whose acceptance says nothing about trained models.  Every line is also appended to ``--out``.
 
     python scripts/decode_bench.py --speculative --out profiles/decode_speculative.txt
+    python scripts/decode_bench.py --speculative --temperature 0.8 --out profiles/decode_speculative_sampling.txt
+
+``--speculative --temperature T`` (T > 0): the sampled round of speculative SAMPLING instead: the draft's
+K + 1 sampler launches, the verify launches of ``ops.speculative_verify`` and the composed ATen verification
+of the same rule on the same logits (alternated in one process), then ``generate`` with and without the draft.
 """
 
 import argparse
@@ -248,6 +253,111 @@ def speculative(m, d, names, batches, out_path, prompt=128, new=128, rounds=3, r
         d.clear_decode_graphs()
 
 
+def _composed_verify(tl, dl, drafts, temperature, top_k, top_p, u):
+    """The accept / resample rule of ``ops.speculative_verify`` composed from ATen ops on the device (a sort, a
+    softmax and a cumsum per row for the filters, as ``decoding._sample`` has them; inside tie groups it may
+    differ from the kernel) — what verifying costs without the kernel.  No host value: capturable."""
+    B, K1, V = tl.shape
+    K = K1 - 1
+
+    def probs(x):
+        x = x.float() / temperature
+        if top_k is not None and top_k < V:
+            x = x.masked_fill(x < torch.topk(x, top_k, dim=-1).values[..., -1:], float("-inf"))
+        if top_p is not None and top_p < 1.0:
+            srt, idx = torch.sort(x, dim=-1, descending=True)
+            sm = torch.softmax(srt, -1)
+            drop = sm.cumsum(-1) - sm >= top_p
+            drop[..., 0] = False
+            x = torch.full_like(x, float("-inf")).scatter(-1, idx, srt.masked_fill(drop, float("-inf")))
+        return torch.softmax(x, -1)
+
+    p, q = probs(tl), probs(dl)
+    at = drafts.unsqueeze(-1)
+    pd, qd = p[:, :K].gather(2, at)[..., 0], q.gather(2, at)[..., 0]
+    ok = (qd > 0) & (u[:, :K, 0] * qd < pd)
+    res = (p[:, :K] - q).clamp_(min=0)
+    res = torch.where(res.sum(-1, keepdim=True) > 0, res, p[:, :K])
+    w = torch.cat([res, p[:, K:]], 1)
+    cdf = w.cumsum(-1)
+    cand = (cdf > u[..., 1:] * cdf[..., -1:]).to(torch.int8).argmax(-1)
+    matched = ok.long().cumprod(1).sum(1)
+    j = torch.arange(K1, device=tl.device).view(1, K1)
+    a = matched.view(B, 1)
+    padded = torch.cat([drafts, torch.zeros_like(drafts[:, :1])], 1)
+    return torch.where(j < a, padded, torch.where(j == a, cand, torch.zeros_like(cand))), matched
+
+
+def speculative_sampled(m, d, names, batches, out_path, temperature, prompt=128, new=128, rounds=3, K=4,
+                        top_k=50, top_p=0.95):
+    """What a SAMPLED speculative round costs (``--speculative --temperature T``): per batch, on the two models'
+    own logits after the prompt, µs per call inside a captured graph of 20 calls, alternated over ``rounds``:
+    the K + 1 native sampler launches of the draft tokens, the verify launches (``ops.speculative_verify``) and
+    the composed ATen verification of the same rule on the same logits; then ``generate`` end to end."""
+    from replicann_amd import ops
+    from replicann_amd.models.decoding import KVCache
+    from replicann_amd.ops import rng
+    dev = torch.device("cuda")
+    sink = open(out_path, "a") if out_path else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    emit({"bench": "speculative sampling", "target": names[0], "draft": names[1], "prompt": prompt, "dtype": "bf16",
+          "weights": "random init", "draft_k": K, "temperature": temperature, "top_k": top_k, "top_p": top_p,
+          "rounds": rounds})
+    V = m.config.vocab_size
+    for B in batches:
+        idx = torch.randint(0, V, (B, prompt), device=dev)
+        cache = KVCache(m.config.n_layer, prompt + 64)
+        m.decode_step(idx, cache, lens=[prompt] * B)
+        win = torch.randint(0, V, (B, K + 1), device=dev)
+        tl = m.decode_window_logits(win, cache)  # (B, K+1, V): the padded LM head's slice
+        dl = torch.empty(B, K, -(-V // 8) * 8, dtype=tl.dtype, device=dev)[..., :V]
+        dl.copy_(d(win[:, :K])[..., :V])  # the draft model's logits on the same tokens
+        drafts = torch.stack([ops.sample_logits(dl[:, i], temperature, top_k, top_p, seed_buf=rng.next_seed(dev))[0][:, 0]
+                              for i in range(K)], 1)
+        u = torch.rand(B, K + 1, 2, device=dev)
+        seed = rng.next_seed(dev)
+        cases = {
+            f"{K + 1} sampler launches": lambda: [ops.sample_logits(tl[:, i], temperature, top_k, top_p, seed_buf=seed)
+                                                   for i in range(K + 1)],
+            "verify kernel": lambda: ops.speculative_verify(tl, dl, drafts, temperature, top_k, top_p, u=u,
+                                                             check_drafts=False),
+            "verify composed (ATen)": lambda: _composed_verify(tl, dl, drafts, temperature, top_k, top_p, u),
+        }
+        us = {k: [] for k in cases}
+        for r in range(rounds):
+            for k, fn in cases.items():
+                us[k].append(_op_us(fn))
+                emit({"batch": B, "case": k, "round": r, "us_per_call": round(us[k][-1], 2)})
+        kt, mt = ops.speculative_verify(tl, dl, drafts, temperature, top_k, top_p, u=u, check_drafts=False)
+        ct, cm = _composed_verify(tl, dl, drafts, temperature, top_k, top_p, u)
+        emit({"summary": "median us per call", "batch": B, **{k: round(sorted(v)[len(v) // 2], 2) for k, v in us.items()},
+              "composed spread us": round(max(us["verify composed (ATen)"]) - min(us["verify composed (ATen)"]), 2),
+              "kernel and composed agree on matched": int((mt == cm).sum()), "of rows": B,
+              "mean matched": round(float(mt.float().mean()), 3)})
+        del cache, tl, dl
+        runs = {"plain sampled (native)": dict(), f"draft_k={K}": dict(draft=d, draft_k=K)}
+        kw0 = dict(temperature=temperature, top_k=top_k, top_p=top_p, sampler="native", graph=True)
+        for k, kw in runs.items():
+            m.generate(idx, new, **kw0, **kw)  # warm-up: capture
+            stats = {}
+            total, _ = _timed(lambda: m.generate(idx, new, **kw0, **kw, **({"stats": stats} if kw else {})))
+            rec = {"batch": B, "end to end": k, "weights": "random init", "new_tokens": new, "total_ms": round(total * 1e3, 2),
+                   "generated_tokens_per_s": round(B * new / total, 1)}
+            if kw:
+                rec["rounds"] = stats["rounds"]
+                rec["mean accepted per drafted"] = round(float(stats["accepted"].sum()) / max(1, int(stats["drafted"].sum())), 4)
+            emit(rec)
+        m.clear_decode_graphs()
+        d.clear_decode_graphs()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2-small")
@@ -259,6 +369,9 @@ def main():
     ap.add_argument("--speculative", action="store_true", help="the cost of a speculative round (see above)")
     ap.add_argument("--draft-model", default="gpt2-small")
     ap.add_argument("--out", default="", help="--speculative: also append every line to this file")
+    ap.add_argument("--temperature", type=float, default=0.0,
+                    help="--speculative: > 0 measures the SAMPLED round instead (top_k 50, top_p 0.95, draft_k 4): the "
+                         "sampler launches, the verify kernel against the composed ATen verification, and generate")
     a = ap.parse_args()
     if a.speculative and a.model == "gpt2-small":
         a.model = "gpt2-medium"  # the default pair: small drafts for medium
@@ -283,6 +396,9 @@ def main():
             p.data = p.data.to(torch.bfloat16)
         d.eval()
         with torch.no_grad():
+            if a.temperature > 0:
+                return speculative_sampled(m, d, (a.model, a.draft_model), [int(b) for b in a.batches.split(",")],
+                                           a.out, a.temperature, prompt=a.prompt, new=a.new)
             return speculative(m, d, (a.model, a.draft_model), [int(b) for b in a.batches.split(",")], a.out,
                                prompt=a.prompt, new=a.new)
     if a.ragged:
