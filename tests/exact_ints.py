@@ -42,6 +42,10 @@ LAYOUTS = [(False, False), (False, True), (True, False), (True, True)]  # (ta, t
 SKINNY = [(M, N, K) for M in (1, 5, 33, 64) for N, K in ((776, 1088), (200, 520))]
 # partial last 128-row and 256-row tiles: rows >= M must contribute nothing to the bias gradient
 ACT_BWD = [(4600, 3072, 72), (300, 264, 192)]
+# more than 1024 column-partial rows (gemm_plan.h gemm_colpart_rows: cfg 9 writes two per 256-row tile, 1028 here;
+# the 128-row configs 1027), the first size at which the column reduction is the ticketed rn_colsum_k and not the
+# one-block rn_colsum1_k.  K = 8: |a·b| <= 8, the column sums stay below 8 · 131400 < 2^24
+ACT_BWD_TICKET = (131400, 72, 8)
 # (M, N, K, density): |h| <= 64 needs a thinner operand at K = 520
 GELU = [(200, 72, 96, 1.0), (1000, 384, 520, 0.5), (8200, 2056, 72, 1.0)]
 FP8_FWD = [(1000, 776, 512), (8200, 2056, 2048)]  # the second takes the K >= 2048 persistent path

@@ -90,6 +90,10 @@ def test_act_bwd(M, N, K, act):
     E.case_act_bwd(CPU, M, N, K, act, variants=((-1, 0),), strided=((-1, 0, 16), (-1, 0, 4)))
 
 
+def test_act_bwd_ticket_shape():
+    E.case_act_bwd(CPU, *E.ACT_BWD_TICKET, 3, variants=((-1, 0),), strided=())
+
+
 def test_bias_grad_unaligned():
     E.case_bias_grad_unaligned(CPU, 300, 264)
 

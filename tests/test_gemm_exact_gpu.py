@@ -118,6 +118,17 @@ def test_act_bwd_bias_grad_captured(cuda, M, N, K):
     E.assert_bitwise(bg.view(1, -1), exp_bg.view(1, -1), what="captured cfg -1: bias_grad")
 
 
+def test_act_bwd_bias_grad_ticket_reduction(cuda):
+    """More than 1024 column-partial rows: rn_colreduce_seg leaves the one-block rn_colsum1_k for rn_colsum_k,
+    whose blocks hand their slab sums over write-through, take an arrival ticket, and whose last arriver sums the
+    slabs and re-arms the counter.  Only the configs that emit column partials; twice in one process: the second
+    run passes only if every counter was reset."""
+    M, N, K = E.ACT_BWD_TICKET
+    assert 2 * ((M + 255) // 256) > 1024 and (M + 127) // 128 > 1024  # gemm_colpart_rows: cfg 9, the 128-row configs
+    for _ in range(2):
+        E.case_act_bwd(cuda, M, N, K, 3, variants=E.BWD_COLPART, strided=())
+
+
 def test_bias_grad_unaligned_rows(cuda):
     E.case_bias_grad_unaligned(cuda, 300, 264)
 

@@ -401,8 +401,9 @@ def test_layernorm_passthrough_producer_bias(cuda, M, E):
 @pytest.mark.parametrize("C,M", [(64, 3000), (200, 3000), (2304, 3000), (50304, 3000), (64, 40000), (96, 20000)])
 def test_bias_grad_column_reduction(cuda, C, M):
     """Deterministic column sums of the row-split partials (the splitter makes <= 512 of them, so the
-    one-pass kernel; up to 512 rows at M=40000, C=64) — bitwise repeatable.  The two-stage last-block
-    kernel (> 512 partial rows) is exercised by the LayerNorm-backward tests."""
+    one-pass kernel rn_colsum1_k; up to 512 rows at M=40000, C=64) — bitwise repeatable.  The LayerNorm
+    backward also stops at 512 partial rows; the ticketed last-block kernel rn_colsum_k takes over above 1024
+    partial rows only: tests/test_gemm_exact_gpu.py::test_act_bwd_bias_grad_ticket_reduction."""
     torch.manual_seed(6)
     dy = bf(M, C)
     _, db1 = torch.ops.replicann.bias_act_grad(dy, None, 0, True, None)
