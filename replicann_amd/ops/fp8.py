@@ -45,21 +45,22 @@ FP8_MLP_FUSE = True
 
 
 def pow2_ceil(s):
-    """The smallest power of two >= s (float32, exact; 1 for s <= 0): every fp8 scale is one, so the
+    """The smallest power of two >= s (float32, exact; 1 for s <= 0; the smallest normal, 2^-126, for a
+    subnormal s, whose own power of two would have no finite reciprocal): every fp8 scale is one, so the
     one-wave-per-SIMD GEMM can feed the tensors' exponents to the scaled MFMA (csrc/kernels/fp8.hip,
     pow2_ceil)."""
     s = torch.as_tensor(s, dtype=torch.float32)
     if not bool(s > 0):
         return torch.tensor(1.0)
     m, e = torch.frexp(s)  # s = m · 2^e, m in [0.5, 1)
-    e = torch.where(m == 0.5, e - 1, e)
+    e = torch.where(m == 0.5, e - 1, e).clamp(min=-126)
     return torch.ldexp(torch.tensor(1.0), e).float()
 
 
 def _pow2_ceil_pos(s):
     """Element-wise pow2_ceil of the positive entries of a scale tensor (others unchanged)."""
     m, e = torch.frexp(s)
-    e = torch.where(m == 0.5, e - 1, e)
+    e = torch.where(m == 0.5, e - 1, e).clamp(min=-126)
     return torch.where(s > 0, torch.ldexp(torch.ones_like(s), e), s)
 
 

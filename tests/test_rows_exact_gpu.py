@@ -6,8 +6,8 @@ bitwise; elsewhere each element is held to a bound derived in the case's docstri
 template instantiation and the branch its shape reaches.  The CPU tier, tests/test_exact_rows.py, runs the same
 cases on an emulation and shows that each check catches a slip the whole-tensor norm lets through.
 
-What these tests do not hold: the e4m3 / e5m2 bytes of the q8 instantiations (tests/test_fp8_ln_q8_gpu.py and the
-fp8 tests hold those); rn_colred1_k / rn_colred2_k, which need more than 4096 column blocks and more than 1024
+What these tests do not hold: the e4m3 / e5m2 bytes of the q8 instantiations (tests/test_fp8_ln_q8_gpu.py holds them
+bitwise to the quantisers, which tests/test_fp8_exact_gpu.py holds to the OCP formats); rn_colred1_k / rn_colred2_k, which need more than 4096 column blocks and more than 1024
 partial rows at once (docs/DESIGN.md §7).  The ticket kernel rn_colsum_k is reached by
 tests/test_gemm_exact_gpu.py::test_act_bwd_bias_grad_ticket_reduction."""
 
