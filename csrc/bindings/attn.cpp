@@ -1,6 +1,7 @@
 // Attention and decoding bindings: attn_fwd and the backward forms, attn_decode, attn_window, linear_kv,
-// sample_logits, replicann_spec::verify (kernels: attention*.hip, attention_decode.hip, attention_window.hip,
-// gemm_skinny.hip, sampling.hip, spec_verify.hip).  Not named attention.cpp:
+// sample_logits, replicann_spec::verify, replicann_kv8::attn_decode / append (kernels: attention*.hip,
+// attention_decode.hip, attention_decode_kv8.hip, attention_window.hip, gemm_skinny.hip, sampling.hip,
+// spec_verify.hip).  Not named attention.cpp:
 // the build keys its per-unit compiler flags by file stem, and those of attention.hip are for device code.
 #include "binding_util.h"
 #include "rn_api.h"
@@ -122,6 +123,81 @@ Tensor attn_window(const Tensor& qkv, Tensor& kv, const Tensor& pos, double scal
                                   (float)scale, cur_stream());
     TORCH_CHECK(rc == 0, "attn_window: unsupported shape T=", T, " D=", D, " L=", L);
     return o;
+}
+
+// ---- the fp8 KV cache (attention_decode_kv8.hip): kv8 (B, L, 2, H, 64) uint8 e4m3 bytes, kv_scale (B, L, 2, H) fp32,
+// pos 1 or B int32 / int64 write rows (clamped to [0, L] on the device)
+
+// the checks the two ops share; returns kv8's byte strides (batch, row, k|v, head)
+std::vector<long> kv8_check(const char* op, const Tensor& x, const Tensor& kv8, const Tensor& kv_scale, const Tensor& pos,
+                            int64_t B, int64_t H, int64_t D) {
+    TORCH_CHECK(kv8.scalar_type() == at::kByte && kv8.dim() == 5 && kv8.size(0) == B && kv8.size(2) == 2 &&
+                    kv8.size(3) == H && kv8.size(4) == D,
+                op, ": kv8 must be uint8 (B, L, 2, H, D) for ", x.sizes(), ", got ", kv8.sizes());
+    const int64_t L = kv8.size(1);
+    TORCH_CHECK(D == 64, op, ": head size ", D, " (64 only)");
+    TORCH_CHECK(L >= 1 && H >= 1 && B * H <= (int64_t)1 << 30, op, ": cache shape out of range");
+    TORCH_CHECK(kv_scale.scalar_type() == at::kFloat && kv_scale.is_contiguous() && kv_scale.dim() == 4 &&
+                    kv_scale.size(0) == B && kv_scale.size(1) == L && kv_scale.size(2) == 2 && kv_scale.size(3) == H,
+                op, ": kv_scale must be a contiguous float32 (B, L, 2, H) tensor, got ", kv_scale.sizes());
+    TORCH_CHECK(pos.dim() == 1 && (pos.size(0) == 1 || pos.size(0) == B) && pos.is_contiguous(),
+                op, ": pos must be a contiguous tensor of 1 or B values, got ", pos.sizes());
+    TORCH_CHECK(pos.scalar_type() == at::kInt || pos.scalar_type() == at::kLong,
+                op, ": pos must be int32 or int64, got ", pos.scalar_type());
+    TORCH_CHECK(kv8.device() == x.device() && kv_scale.device() == x.device() && pos.device() == x.device(),
+                op, ": every tensor must be on one device");
+    // the kernels move 16-B vectors: base pointers and every non-unit stride 16-B aligned
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && x.stride(4) == 1 &&
+                    reinterpret_cast<uintptr_t>(kv8.data_ptr()) % 16 == 0 && kv8.stride(4) == 1,
+                op, ": the inputs need 16-byte aligned bases and a contiguous head dimension");
+    std::vector<long> cs;
+    for (int d = 0; d < 4; ++d) {
+        TORCH_CHECK(x.stride(d) % 8 == 0 && x.stride(d) >= 0, op, ": input strides must be multiples of 8 elements");
+        TORCH_CHECK(kv8.stride(d) % 16 == 0 && kv8.stride(d) >= 0, op, ": kv8 strides must be multiples of 16 bytes");
+        cs.push_back(kv8.stride(d));
+    }
+    // the append writes through kv8's strides: its rows must not overlap
+    TORCH_CHECK(kv8.stride(3) >= D && kv8.stride(2) >= H * kv8.stride(3) && kv8.stride(1) >= 2 * kv8.stride(2) &&
+                    (B == 1 || kv8.stride(0) >= L * kv8.stride(1)),
+                op, ": kv8 must be a dense (B, L, 2, H, D) layout, got strides ", kv8.strides());
+    return cs;
+}
+
+// one-token attention over the fp8 cache with the append folded in: qkv (B, 1, 3, H, 64) bf16, possibly a strided
+// view of the projection output -> o (B, 1, H, 64).  The new K / V rows are quantised and, if pos < L, written to
+// row pos; the query attends rows 0 .. pos-1 and the new row.
+Tensor attn_decode_kv8(const Tensor& qkv, Tensor& kv8, Tensor& kv_scale, const Tensor& pos, double scale) {
+    CHECK_CUDA(qkv); CHECK_BF16(qkv); CHECK_CUDA(kv8); GUARD(qkv);
+    TORCH_CHECK(qkv.dim() == 5 && qkv.size(1) == 1 && qkv.size(2) == 3,
+                "attn_decode_kv8: qkv must be (B, 1, 3, H, D), got ", qkv.sizes());
+    const int64_t B = qkv.size(0), H = qkv.size(3), D = qkv.size(4);
+    const std::vector<long> cs = kv8_check("attn_decode_kv8", qkv, kv8, kv_scale, pos, B, H, D);
+    const int64_t L = kv8.size(1);
+    TORCH_CHECK(L <= 1024, "attn_decode_kv8: cache length ", L, " outside 1..1024");
+    Tensor o = at::empty({B, 1, H, D}, qkv.options());
+    if (B == 0) return o;
+    const long qs[3] = {(long)qkv.stride(0), (long)qkv.stride(2), (long)qkv.stride(3)};
+    const int rc = rn_attn_decode_kv8(qkv.data_ptr(), kv8.data_ptr(), kv_scale.data_ptr<float>(), pos.data_ptr(),
+                                      pos.scalar_type() == at::kLong ? 1 : 0, (int)pos.size(0), o.data_ptr(), (int)B,
+                                      (int)H, (int)L, (int)D, qs, cs.data(), (float)scale, cur_stream());
+    TORCH_CHECK(rc == 0, "attn_decode_kv8: unsupported shape D=", D, " L=", L);
+    return o;
+}
+
+// the prefill's append: kv_new (B, T, 2, H, 64) bf16 (a strided view is fine); rows pos[b] + i < L are quantised
+// and written, the others skipped
+void kv8_append(const Tensor& kv_new, Tensor& kv8, Tensor& kv_scale, const Tensor& pos) {
+    CHECK_CUDA(kv_new); CHECK_BF16(kv_new); CHECK_CUDA(kv8); GUARD(kv_new);
+    TORCH_CHECK(kv_new.dim() == 5 && kv_new.size(2) == 2, "kv8_append: kv_new must be (B, T, 2, H, D), got ",
+                kv_new.sizes());
+    const int64_t B = kv_new.size(0), T = kv_new.size(1), H = kv_new.size(3), D = kv_new.size(4);
+    const std::vector<long> cs = kv8_check("kv8_append", kv_new, kv8, kv_scale, pos, B, H, D);
+    if (B == 0 || T == 0) return;
+    const long ns[4] = {(long)kv_new.stride(0), (long)kv_new.stride(1), (long)kv_new.stride(2), (long)kv_new.stride(3)};
+    const int rc = rn_kv8_append(kv_new.data_ptr(), kv8.data_ptr(), kv_scale.data_ptr<float>(), pos.data_ptr(),
+                                 pos.scalar_type() == at::kLong ? 1 : 0, (int)pos.size(0), (int)B, (int)T, (int)H,
+                                 (int)kv8.size(1), (int)D, ns, cs.data(), cur_stream());
+    TORCH_CHECK(rc == 0, "kv8_append: unsupported shape ", kv_new.sizes(), " into ", kv8.sizes());
 }
 
 // fused token sampler (sampling.hip): logits (B, V) bf16 / fp32 with a unit column stride and a row
@@ -373,6 +449,17 @@ TORCH_LIBRARY_FRAGMENT(replicann_spec, m) {
 
 TORCH_LIBRARY_IMPL(replicann_spec, CUDA, m) {
     m.impl("verify", &spec_verify);
+}
+
+// the fp8 KV cache: its own namespace as well (every list above is pinned by a test)
+TORCH_LIBRARY_FRAGMENT(replicann_kv8, m) {
+    m.def("attn_decode(Tensor qkv, Tensor(a!) kv8, Tensor(b!) kv_scale, Tensor pos, float scale) -> Tensor");
+    m.def("append(Tensor kv_new, Tensor(a!) kv8, Tensor(b!) kv_scale, Tensor pos) -> ()");
+}
+
+TORCH_LIBRARY_IMPL(replicann_kv8, CUDA, m) {
+    m.impl("attn_decode", &attn_decode_kv8);
+    m.impl("append", &kv8_append);
 }
 
 TORCH_LIBRARY_IMPL(replicann, CUDA, m) {

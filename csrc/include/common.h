@@ -57,6 +57,17 @@ RN_DEV float wave_max(float v) {
     return v;
 }
 
+// The fp8 scale rule: the smallest power of two >= s (1 for s <= 0 or NaN; inf passes through; a subnormal s
+// gives the smallest normal, whose reciprocal is finite).  Used by the quantisers (fp8.hip) and the fp8 KV cache.
+RN_DEV float pow2_ceil(float s) {
+    if (!(s > 0.f)) return 1.f;
+    uint32_t u = __float_as_uint(s);
+    const uint32_t e = u & 0x7F800000u;
+    if (e == 0x7F800000u) return s;  // inf / nan pass through
+    u = (u & 0x007FFFFFu) ? e + 0x00800000u : e;
+    return __uint_as_float(u ? u : 0x00800000u);  // (subnormal: the smallest normal)
+}
+
 // Block-wide sum for blockDim.x <= 1024 (scratch: >= 16 floats of LDS).
 RN_DEV float block_sum(float v, float* scratch) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;

@@ -223,6 +223,20 @@ int rn_attn_decode(const void* q, const void* k, const void* v, const float* mas
 int rn_attn_window(const void* qkv, void* kv, const void* pos, int pos64, void* o, int B, int T, int H,
                    int L, int D, const long* qs, const long* cs, float scale, hipStream_t st);
 
+// ------------------------------------------------------------------ attention_decode_kv8.hip
+// The fp8 (OCP e4m3) KV cache: kv8 (B, L, 2, H, 64) bytes with the BYTE strides cs (batch, row, k|v, head, each a
+// multiple of 16), kv_scale (B, L, 2, H) fp32 contiguous, one power-of-two scale per 64-element head row.
+// pos: pos_n (1 or B) write rows, int64 if pos64 else int32, clamped to [0, L] on the device.
+// One-token attention with the append folded in: qkv (B, 1, 3, H, 64) bf16 with the element strides qs (batch,
+// q|k|v, head); the new K / V rows are quantised, written to row pos if pos < L, and the query attends rows
+// 0 .. pos-1 plus the new row; o (B, 1, H, 64) contiguous.  L <= 1024.  Returns -1 for what it does not take.
+int rn_attn_decode_kv8(const void* qkv, void* kv8, float* kv_scale, const void* pos, int pos64, int pos_n, void* o,
+                       int B, int H, int L, int D, const long* qs, const long* cs, float scale, hipStream_t st);
+// The prefill's append: kv_new (B, T, 2, H, 64) bf16 with the element strides ns (batch, token, k|v, head); rows
+// pos[b] + i < L are quantised and written, the others skipped.  Any L.
+int rn_kv8_append(const void* kv_new, void* kv8, float* kv_scale, const void* pos, int pos64, int pos_n, int B, int T,
+                  int H, int L, int D, const long* ns, const long* cs, hipStream_t st);
+
 // ------------------------------------------------------------------ sampling.hip
 // logits (B, V) bf16 / fp32 with row stride ld >= V; exactly one of u (B fp32 in [0, 1)) and seed
 // (row b draws hash_uniform(*seed, b)); params: 3 fp32 on the device (temperature, top_k, top_p)

@@ -22,15 +22,8 @@ constexpr float E4M3_MAX = 448.f;
 // q = x / s stays within the format's range), so that a scale is an exact E8M0 exponent: the
 // one-wave-per-SIMD GEMM (gemm_w1.h) feeds the two tensors' exponents to the scaled MFMA's block-
 // scale operands instead of multiplying every output by sa·sb (the same bits as the multiply: a
-// product of powers of two is exact).
-__device__ inline float pow2_ceil(float s) {
-    if (!(s > 0.f)) return 1.f;
-    uint32_t u = __float_as_uint(s);
-    const uint32_t e = u & 0x7F800000u;
-    if (e == 0x7F800000u) return s;  // inf / nan pass through
-    u = (u & 0x007FFFFFu) ? e + 0x00800000u : e;
-    return __uint_as_float(u ? u : 0x00800000u);  // (subnormal: the smallest normal)
-}
+// product of powers of two is exact).  The rule itself is pow2_ceil (common.h; the fp8 KV cache's row scales
+// follow it too).
 
 __global__ void __launch_bounds__(256) amax_k(const bf16* __restrict__ x, long n, float* __restrict__ state) {
     __shared__ float sm[16];

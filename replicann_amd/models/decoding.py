@@ -38,11 +38,24 @@ class KVCache:
         Only this mode has the window step (``windowed`` / ``window`` / ``advance`` / ``set_rows``): T
         tokens per row written and attended at each row's own position, committed separately.
     A captured step reads the device tensors by address, so each is allocated once per cache and kept
-    through ``reset()`` and every mode change (the per-sequence triple: until the batch size changes)."""
+    through ``reset()`` and every mode change (the per-sequence triple: until the batch size changes).
 
-    def __init__(self, n_layer, max_len):
+    ``kv_dtype="fp8"`` (default None: the cache above, untouched): ``kv[layer]`` is uint8 (B, max_len, 2, H, D)
+    OCP e4m3 bytes and ``kv_scale[layer]`` fp32 (B, max_len, 2, H) their scales, one power of two per head row
+    (``ops.kv8``: about half the bytes).  The attention layer hands the packed projection output to ``step8``:
+    a one-token step in any mode is one ``ops.attention_decode_kv8`` — append and attention — at the mode's own
+    position tensor, which reads the rows below the position and nothing else, so device mode keeps no key
+    mask; a prefill attends its own unquantised keys / values and stores them with ``ops.kv8_append``.  The
+    window step is not available on an fp8 cache."""
+
+    def __init__(self, n_layer, max_len, kv_dtype=None):
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype must be None or 'fp8', got {kv_dtype!r}")
         self.max_len, self.pos, self.mode = max_len, 0, "host"
+        self.kv_dtype = kv_dtype
         self.kv = [None] * n_layer
+        self.kv_scale = [None] * n_layer  # fp8 only
+        self._host_pos = None  # fp8 only: the host position as a 1-element device tensor (eager steps)
         self._pos1 = self.mask = None  # device mode
         self._rows = self.lens = self.active = None  # per-sequence mode
         self.in_window = False  # inside ``windowed()``: the pass is the window step
@@ -59,6 +72,7 @@ class KVCache:
             self.in_window = False
 
     device_pos = property(lambda self: self.mode != "host")
+    fp8 = property(lambda self: self.kv_dtype == "fp8")
     per_seq = property(lambda self: self.mode == "per_seq")
 
     @property
@@ -67,13 +81,15 @@ class KVCache:
 
     def to_device_position(self):
         """Switch to device mode at the current host position."""
-        if self.mask is None:
+        if self._pos1 is None:
             dev = self.kv[0].device
             self._pos1 = torch.empty(1, dtype=torch.long, device=dev)
-            self.mask = torch.empty(1, 1, self.max_len, device=dev)
+            if not self.fp8:  # the fp8 step reads rows < pos only: no key mask
+                self.mask = torch.empty(1, 1, self.max_len, device=dev)
         self._pos1.fill_(self.pos)
-        self.mask.fill_(float("-inf"))
-        self.mask[..., : self.pos] = 0.0
+        if self.mask is not None:
+            self.mask.fill_(float("-inf"))
+            self.mask[..., : self.pos] = 0.0
         self.mode = "device"
 
     def to_per_sequence(self, lens):
@@ -106,13 +122,17 @@ class KVCache:
             self.lens.copy_(snap[2])
         else:
             self._pos1.fill_(self.pos)
-            self.mask[..., self.pos:] = float("-inf")
+            if self.mask is not None:
+                self.mask[..., self.pos:] = float("-inf")
 
     def begin_step(self, T):
         """Before ``T`` tokens are embedded and appended: device mode opens the mask at the write row,
         the modes with a host position check the capacity."""
         if self.mode == "device":
-            self.mask.index_fill_(2, self._pos1, 0.0)
+            if self.mask is not None:
+                self.mask.index_fill_(2, self._pos1, 0.0)
+            elif T != 1:
+                raise ValueError("an fp8 cache in device mode takes one token per step")
         elif self.mode == "per_seq" and T != 1:
             raise ValueError("a cache in per-sequence mode takes one token per row and step")
         elif self.pos + T > self.max_len:
@@ -138,6 +158,8 @@ class KVCache:
         queries to the cached rows and the window so far: one ``ops.attention_window``.  The position
         does not move (``advance``): whatever the window wrote past it stays unread."""
         self._need_per_seq("window")
+        if self.fp8:
+            raise ValueError("the window step is not available on an fp8 KV cache")
         return ops.attention_window(qkv, self.kv[layer], self._rows)
 
     def advance(self, counts, bound=None):
@@ -197,6 +219,39 @@ class KVCache:
             buf.scatter_(1, self._rows.view(-1, 1, 1, 1, 1).expand_as(kv), kv)
         return buf[:, :, 0], buf[:, :, 1]
 
+    def step8(self, layer, qkv, causal):
+        """An fp8 cache's append and attention in one: ``qkv`` (B, T, 3, H, D), the packed projection output,
+        -> (B, T, H, D).  T == 1 (every mode): ``ops.attention_decode_kv8`` at the mode's position tensor.  A
+        host-mode prefill at position 0 attends its own unquantised keys / values, then ``ops.kv8_append`` stores
+        the T rows (a ragged one writes junk past lens[b] as the bf16 cache does; it is never read).  T > 1 at a
+        position > 0 (host mode) is the slow composed path: the rows below the position dequantised, this pass's
+        own rows after them, the causal attention, then the append."""
+        B, T, _, H, D = qkv.shape
+        if self.kv[layer] is None:
+            if self.mode != "host":
+                raise ValueError("an fp8 KV cache is allocated by a host-mode pass (a prefill)")
+            # rows at or past a position are never read, but a fresh buffer should not look like data
+            self.kv[layer] = torch.zeros(B, self.max_len, 2, H, D, dtype=torch.uint8, device=qkv.device)
+            self.kv_scale[layer] = torch.ones(B, self.max_len, 2, H, dtype=torch.float32, device=qkv.device)
+        kv8, sc = self.kv[layer], self.kv_scale[layer]
+        if self.mode == "host":
+            if self._host_pos is None:
+                self._host_pos = torch.empty(1, dtype=torch.long, device=qkv.device)
+            pos = self._host_pos.fill_(self.pos)  # host mode is eager only
+        else:
+            pos = self.pos_t
+        if T == 1:
+            return ops.attention_decode_kv8(qkv, kv8, sc, pos)
+        if self.mode != "host":
+            raise ValueError("an fp8 KV cache takes several tokens per step in host mode only")
+        q, k, v = qkv.unbind(2)
+        if self.pos > 0:
+            old = ops.kv8_dequantize(kv8[:, : self.pos], sc[:, : self.pos]).to(qkv.dtype)
+            k, v = torch.cat([old[:, :, 0], k], 1), torch.cat([old[:, :, 1], v], 1)
+        a = ops.attention(q, k, v, causal=causal)
+        ops.kv8_append(qkv[:, :, 1:3], kv8, sc, pos)
+        return a
+
     def attend(self, q, k, v, causal):
         """Attention of this step's queries (B, T, H, D) over the key / value views of the append."""
         if self.mode == "per_seq":  # each row reads its own lens[b] keys
@@ -236,7 +291,8 @@ def _sample(logits, temperature, top_k, generator, top_p=None):
 
 
 # captured decode steps kept per model (least recently used evicted first): each holds a KV cache of
-# 2 · n_layer · B · length · n_embd elements (≈ 2.4 GB for GPT-2-small at B = 64, length 1024)
+# 2 · n_layer · B · length · n_embd elements (≈ 2.4 GB for GPT-2-small at B = 64, length 1024; ≈ 1.3 GB with
+# kv_dtype="fp8": a byte per element and 4 bytes of scale per 64)
 DECODE_GRAPHS_MAX = int(os.environ.get("REPLICANN_DECODE_GRAPHS", "4"))
 DECODE_LEN_BUCKET = 64  # cache lengths are rounded up to this (capped at block_size): one graph per bucket
 DECODE_EOS_CHECK = 8  # ragged generate: "has every row finished?" is asked of the device every this many steps
@@ -247,12 +303,12 @@ class _GraphRegistry(dict):
     (batch, cache length, dtype, device, parameter storage[, "ragged" for the per-sequence step]
     [, "sampler" for a step captured together with the native sampler][, "window", T for the window step of
     T tokens per row: its output is the greedy ids (B, T)][, "logits" for the window step whose output is the
-    logits (B, T, vocab) instead]) → (cache, graph, token buffer, logits), so a serving loop captures once per (batch, length bucket).  A sampler entry holds the
+    logits (B, T, vocab) instead][, "fp8" for a step over an fp8 KV cache, always last]) → (cache, graph, token buffer, logits), so a serving loop captures once per (batch, length bucket).  A sampler entry holds the
     sampled tokens (B, 1) in place of the logits, then the device tensor its settings are read from:
     one graph whatever the temperature / top_k / top_p.
     At most DECODE_GRAPHS_MAX (REPLICANN_DECODE_GRAPHS, default 4) are kept; each holds its KV cache."""
 
-    def lookup(self, model, B, L, ragged, use, sampler=False, window=None, logits=False):
+    def lookup(self, model, B, L, ragged, use, sampler=False, window=None, logits=False, kv_dtype=None):
         """(key, its stored entry — now the most recently used — or None).  The parameters' storage
         is part of the key: a graph reads them by address, so entries captured before a parameter was
         re-assigned (p.data = ...) are dropped here, whether or not this call will ``use`` a graph."""
@@ -261,6 +317,7 @@ class _GraphRegistry(dict):
         key += ("sampler",) if sampler else ()
         key += ("window", window) if window else ()  # the captured window step of this many tokens per row
         key += ("logits",) if logits else ()  # ... returning its logits, not the greedy ids
+        key += (kv_dtype,) if kv_dtype else ()  # an fp8 cache's step never aliases the bf16 one
         for k in [k for k in self if k[4] != sig]:
             del self[k]
         entry = self.pop(key, None) if use else None
@@ -529,7 +586,7 @@ class _StepDriver:
     """One ``generate`` call's cache and one-token step.  With ``graph``, an earlier call's cache and
     captured step of the same key are reused; failing that the first ``step`` captures (and stores) one."""
 
-    def __init__(self, model, B, length, ragged, graph, sampling, native):
+    def __init__(self, model, B, length, ragged, graph, sampling, native, kv_dtype=None):
         c = model.config
         if graph or ragged:  # one captured step (and cache) serves every length of a bucket
             length = min(c.block_size, -(-length // DECODE_LEN_BUCKET) * DECODE_LEN_BUCKET)
@@ -538,8 +595,9 @@ class _StepDriver:
         self.sampling, self.native = sampling, native
         self.fused = native and graph  # the sampler is part of the captured step
         self.settings_sent = False  # fused: has this call written its settings into the graph's tensor?
-        self.key, self.entry = self.graphs.lookup(model, B, length, ragged, graph, sampler=self.fused)
-        self.cache = KVCache(c.n_layer, length) if self.entry is None else self.entry[0]
+        self.key, self.entry = self.graphs.lookup(model, B, length, ragged, graph, sampler=self.fused,
+                                                  kv_dtype=kv_dtype)
+        self.cache = KVCache(c.n_layer, length, kv_dtype) if self.entry is None else self.entry[0]
         self.cache.reset()
 
     def step(self, tok):
@@ -581,7 +639,7 @@ class _StepDriver:
 @torch.no_grad()
 def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=None, generator=None, graph=None,
              prompt_lens=None, eos_token_id=None, pad_token_id=None, sampler="torch", draft=None, draft_k=4,
-             stats=None):
+             stats=None, kv_dtype=None):
     """Autoregressive sampling with a KV cache: ``idx`` (B, T0) prompt → (B, T0 + max_new_tokens).
     ``temperature`` 0 = greedy; ``top_k`` / ``top_p`` restrict sampling.  One prefill pass over the prompt, then one-token steps whose
     attention reads the cached keys / values (no recomputation of the prefix).  ``graph``
@@ -621,13 +679,24 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     p), so every committed token is distributed as this model's own sampling; ``accept`` applies the same
     cuts.  The verifier's two launches are issued after the window step (with ``graph``: after its replay, not
     captured with it); the randomness is that of ``sampler="native"``.  The caches hold ``draft_k`` rows more than the
-    tokens: prompt + ``max_new_tokens`` + ``draft_k`` must fit both models' block_size."""
+    tokens: prompt + ``max_new_tokens`` + ``draft_k`` must fit both models' block_size.
+
+    ``kv_dtype="fp8"`` (default None: the cache in the model's dtype): the KV cache is kept as OCP e4m3 bytes
+    with one power-of-two scale per 64-element head row (``decoding.KVCache``, ``ops.kv8``) — 0.53 of the
+    bytes, in memory and per step — and the one-token step's attention quantises and appends the new row
+    itself (``ops.attention_decode_kv8``).  The prefill attends its own unquantised keys / values.  Every mode
+    above works with it except ``draft``, which raises: the window step has no fp8 form."""
     B, T0 = idx.shape
     ragged = prompt_lens is not None or eos_token_id is not None
     if top_p is not None and not 0.0 < top_p <= 1.0:
         raise ValueError(f"top_p must be in (0, 1], got {top_p}")
     if sampler not in ("torch", "native"):
         raise ValueError(f"sampler must be 'torch' or 'native', got {sampler!r}")
+    if kv_dtype not in (None, "fp8"):
+        raise ValueError(f"kv_dtype must be None or 'fp8', got {kv_dtype!r}")
+    if draft is not None and kv_dtype is not None:
+        raise ValueError("generate(draft=...) needs the window step, which an fp8 KV cache does not have: "
+                         "kv_dtype must be None")
     native = sampler == "native"
     if native and generator is not None and model.wte.is_cuda:
         raise ValueError("sampler='native' on a GPU model draws from the device seed stream "
@@ -659,7 +728,7 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     model.eval()
     try:
         driver = _StepDriver(model, B, Tm + max_new_tokens, ragged, use_graph,
-                             (temperature, top_k, generator, top_p), native)
+                             (temperature, top_k, generator, top_p), native, kv_dtype)
         if ragged:
             return _ragged_loop(driver, idx[:, :Tm], plens, max_new_tokens, eos_token_id, pad_token_id)
         logits = model.decode_step(idx, driver.cache)

@@ -518,6 +518,9 @@ def generate_main(argv=None):
                          "(--temperature 0: greedy; a temperature > 0 is speculative sampling and needs --sampler native)")
     ap.add_argument("--draft-checkpoint", default=None)
     ap.add_argument("--draft-k", type=int, default=4)
+    ap.add_argument("--kv-dtype", choices=("fp8",), default=None,
+                    help="fp8: keep the KV cache as e4m3 bytes with one scale per head row (about half the bytes; not "
+                         "with --draft-model)")
     a = ap.parse_args(argv)
     if not a.model.startswith("gpt2") or not (a.draft_model or "gpt2").startswith("gpt2"):
         raise SystemExit(f"generate: {a.model} / {a.draft_model} is not an autoregressive GPT-2 model")
@@ -542,6 +545,8 @@ def generate_main(argv=None):
             load_committed(a.draft_model)
             draft = draft.to(torch.bfloat16)
         spec = dict(draft=draft, draft_k=a.draft_k, stats=stats)
+    if a.kv_dtype:
+        spec["kv_dtype"] = a.kv_dtype
     gen = torch.Generator(device=dev).manual_seed(a.seed)
     if a.sampler == "native" and dev.type == "cuda":  # the device seed stream takes the generator's place
         from .ops import rng

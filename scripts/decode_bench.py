@@ -39,6 +39,18 @@ weights, whose acceptance says nothing about trained models.  Every line is also
 ``--speculative --temperature T`` (T > 0): the sampled round of speculative SAMPLING instead: the draft's
 K + 1 sampler launches, the verify launches of ``ops.speculative_verify`` and the composed ATen verification
 of the same rule on the same logits (alternated in one process), then ``generate`` with and without the draft.
+
+``--kv-fp8``: the captured one-token step over the bf16 KV cache against the one over the fp8 cache
+(``generate(kv_dtype="fp8")``), GPT-2-small at batch 64, 128 new tokens after prompts of 128 and of 896 tokens (the
+second fills the 1024-row bucket).  Per prompt the two graphs are alternated in one process after a warm-up of
+each, three rounds of 128 replays from the prompt's position; one line per timed run, then the medians, the spread
+of the rounds, each cache's bytes and the two criteria (prompt 896: fp8 faster by more than the spread; prompt 128:
+at most 1.05x).  Then, inside captured graphs, the two attention kernels (24 calls walking the 12 layers' caches, so
+that the rows come from memory as in the step) and the two QKV projections alone, and the relative L2 between fp8-cache and bf16-cache logits over 12 steps of the tests' tiny model
+(reported, not gated: random weights).  Every line is also appended to ``--out``.
+
+    python scripts/decode_bench.py --kv-fp8 --out profiles/decode_kv_fp8.txt
+    rocprofv3 --kernel-trace --stats ... -- python scripts/decode_bench.py --kv-fp8 --prompts 896 --new 32   # per-kernel times
 """
 
 import argparse
@@ -253,6 +265,100 @@ def speculative(m, d, names, batches, out_path, prompt=128, new=128, rounds=3, r
         d.clear_decode_graphs()
 
 
+def kv_fp8(m, model, out_path, B=64, prompts=(128, 896), new=128, rounds=3):
+    """The captured step over a bf16 cache against the one over an fp8 cache (``--kv-fp8``)."""
+    from replicann_amd import ops
+    from replicann_amd.models import decoding
+    from replicann_amd.models.decoding import KVCache
+    from replicann_amd.models.gpt2 import GPT2, GPT2Config
+    dev = torch.device("cuda")
+    sink = open(out_path, "a") if out_path else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    emit({"bench": "fp8 KV cache", "model": model, "batch": B, "new_tokens": new, "dtype": "bf16", "weights": "random init",
+          "rounds": rounds, "replays_per_timing": new - 1})
+    nl, H = m.config.n_layer, m.config.n_head
+    for prompt in prompts:
+        idx = torch.randint(0, m.config.vocab_size, (B, prompt), device=dev)
+        length = min(m.config.block_size, -(-(prompt + new) // decoding.DECODE_LEN_BUCKET) * decoding.DECODE_LEN_BUCKET)
+        graphs, nbytes = {}, {}
+        for name, kvd in (("bf16 cache", None), ("fp8 cache", "fp8")):
+            c = KVCache(nl, length, kvd)
+            m.decode_step(idx, c)
+            m.decode_step(idx[:, :1], c)  # tunes the one-token GEMM shapes outside the capture
+            c.pos = prompt  # (the row that step wrote is overwritten by the first replay)
+            graphs[name] = (decoding.capture_step(m, c, B)[0], c)
+            nbytes[name] = sum(t.numel() * t.element_size() for t in c.kv + (c.kv_scale if kvd else []))
+        ms = {k: [] for k in graphs}
+        for r in range(rounds):
+            for k, (g, c) in graphs.items():
+                snap = c.snapshot()
+                g.replay()
+                ms[k].append(_replay_ms(g, new - 1))  # rows prompt .. prompt + new - 1
+                c.restore(snap)
+                emit({"prompt": prompt, "cache rows": length, "case": k, "round": r, "ms_per_step": round(ms[k][-1], 4)})
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        spread = max(max(v) - min(v) for v in ms.values())
+        rec = {"summary": "median ms per captured step", "prompt": prompt, **{k: round(v, 4) for k, v in med.items()},
+               "spread of the rounds ms": round(spread, 4), "fp8_over_bf16": round(med["fp8 cache"] / med["bf16 cache"], 4),
+               **{f"{k} bytes": v for k, v in nbytes.items()},
+               "cache bytes fp8_over_bf16": round(nbytes["fp8 cache"] / nbytes["bf16 cache"], 4)}
+        if prompt >= 512:
+            rec["criterion: fp8 faster by more than the spread"] = bool(med["bf16 cache"] - med["fp8 cache"] > spread)
+        else:
+            rec["criterion: fp8 at most 1.05x"] = bool(med["fp8 cache"] <= 1.05 * med["bf16 cache"])
+        emit(rec)
+        # the kernels alone at the prompt's row count: consecutive calls walk the 12 layers' caches (1.3 / 2.4 GB at
+        # 1024 rows), as the step does, so that no call finds its rows in the 256 MiB last-level cache
+        c8, cb = graphs["fp8 cache"][1], graphs["bf16 cache"][1]
+        turn = [0]
+
+        def layer():
+            turn[0] = (turn[0] + 1) % nl
+            return turn[0]
+        pos = torch.full((B,), prompt, device=dev)
+        lens = pos + 1
+        blk = m.h[0].attn
+        with torch.no_grad():
+            qkv = torch.randn(B, 1, 3, H, 64, device=dev).bfloat16()
+            h = torch.randn(B, 1, m.config.n_embd, device=dev).bfloat16()
+            def bf16_attn():
+                kv = cb.kv[layer()]
+                return ops.attention_decode(qkv[:, :, 0], kv[:, :, 0], kv[:, :, 1], lens=lens)
+
+            def fp8_attn():
+                i = layer()
+                return ops.attention_decode_kv8(qkv, c8.kv[i], c8.kv_scale[i], pos)
+
+            emit({"prompt": prompt, "batch": B, "us per call inside a captured graph": "24 calls over the 12 layers' caches",
+                  "attn_decode64_k (bf16 cache, lens)": round(_op_us(bf16_attn, calls=2 * nl), 2),
+                  "attn_decode_kv8_k (fp8 cache, append included)": round(_op_us(fp8_attn, calls=2 * nl), 2),
+                  "QKV GEMM with the append epilogue (linear_kv)": round(_op_us(
+                      lambda: ops.linear_kv_append(h, blk.c_attn.weight, blk.c_attn.bias, cb.kv[0], pos[:1])), 2),
+                  "QKV GEMM (linear)": round(_op_us(lambda: blk.c_attn(h)), 2)})
+        del graphs, c8, cb
+    # what the quantisation does to the logits: the tests' tiny model, 12 teacher-forced steps after a prompt of 20
+    torch.manual_seed(0)
+    tiny = GPT2(GPT2Config.tiny(n_embd=128, n_head=2, n_layer=2, block_size=128)).to(dev)
+    for p in tiny.parameters():
+        p.data = p.data.to(torch.bfloat16)
+    tiny.eval()
+    seq = torch.randint(0, 1000, (3, 32), device=dev)
+    a, b = KVCache(2, 32), KVCache(2, 32, "fp8")
+    errs = []
+    for lo, hi in [(0, 20)] + [(t, t + 1) for t in range(20, 32)]:
+        x, y = tiny.decode_step(seq[:, lo:hi], a).float(), tiny.decode_step(seq[:, lo:hi], b).float()
+        errs.append(float((y - x).norm() / x.norm()))
+    emit({"tiny model (random init), logits with the fp8 cache against the bf16 cache, relative L2": "not gated",
+          "prefill": round(errs[0], 5), "steps": [round(e, 5) for e in errs[1:]], "max": round(max(errs[1:]), 5)})
+
+
 def _composed_verify(tl, dl, drafts, temperature, top_k, top_p, u):
     """The accept / resample rule of ``ops.speculative_verify`` composed from ATen ops on the device (a sort, a
     softmax and a cumsum per row for the filters, as ``decoding._sample`` has them; inside tie groups it may
@@ -367,8 +473,10 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="uniform against ragged decode step (see above)")
     ap.add_argument("--sample", action="store_true", help="sampler='torch' against sampler='native' (see above)")
     ap.add_argument("--speculative", action="store_true", help="the cost of a speculative round (see above)")
+    ap.add_argument("--kv-fp8", action="store_true", help="the captured step over an fp8 KV cache against the bf16 one (see above)")
+    ap.add_argument("--prompts", default="128,896", help="--kv-fp8: the prompt lengths (one alone for a kernel trace)")
     ap.add_argument("--draft-model", default="gpt2-small")
-    ap.add_argument("--out", default="", help="--speculative: also append every line to this file")
+    ap.add_argument("--out", default="", help="--speculative, --kv-fp8: also append every line to this file")
     ap.add_argument("--temperature", type=float, default=0.0,
                     help="--speculative: > 0 measures the SAMPLED round instead (top_k 50, top_p 0.95, draft_k 4): the "
                          "sampler launches, the verify kernel against the composed ATen verification, and generate")
@@ -401,6 +509,9 @@ def main():
                                            a.out, a.temperature, prompt=a.prompt, new=a.new)
             return speculative(m, d, (a.model, a.draft_model), [int(b) for b in a.batches.split(",")], a.out,
                                prompt=a.prompt, new=a.new)
+    if a.kv_fp8:
+        with torch.no_grad():
+            return kv_fp8(m, a.model, a.out, prompts=[int(p) for p in a.prompts.split(",")], new=a.new)
     if a.ragged:
         return ragged(m, a.model, prompt=a.prompt, new=a.new)
     if a.sample:
