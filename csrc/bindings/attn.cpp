@@ -1,7 +1,7 @@
 // Attention and decoding bindings: attn_fwd and the backward forms, attn_decode, attn_window, linear_kv,
-// sample_logits, replicann_spec::verify, replicann_kv8::attn_decode / append (kernels: attention*.hip,
-// attention_decode.hip, attention_decode_kv8.hip, attention_window.hip, gemm_skinny.hip, sampling.hip,
-// spec_verify.hip).  Not named attention.cpp:
+// sample_logits, replicann_spec::verify, replicann_kv8::attn_decode / append, replicann_prefix::attn_decode (kernels:
+// attention*.hip, attention_decode.hip, attention_decode_kv8.hip, attention_decode_prefix.hip, attention_window.hip,
+// gemm_skinny.hip, sampling.hip, spec_verify.hip).  Not named attention.cpp:
 // the build keys its per-unit compiler flags by file stem, and those of attention.hip are for device code.
 #include "binding_util.h"
 #include "rn_api.h"
@@ -198,6 +198,53 @@ void kv8_append(const Tensor& kv_new, Tensor& kv8, Tensor& kv_scale, const Tenso
                                  pos.scalar_type() == at::kLong ? 1 : 0, (int)pos.size(0), (int)B, (int)T, (int)H,
                                  (int)kv8.size(1), (int)D, ns, cs.data(), cur_stream());
     TORCH_CHECK(rc == 0, "kv8_append: unsupported shape ", kv_new.sizes(), " into ", kv8.sizes());
+}
+
+// ---- n samples per prompt over a shared prompt cache (attention_decode_prefix.hip): qkv (B = G n, 1, 3, H, 64) bf16,
+// possibly a strided view of the projection output; prefix_kv (G, P, 2, H, 64) the prompts' rows, read only;
+// prefix_len (G,) and pos (B,) int32 / int64 (clamped to [0, P] / [0, L] on the device); kv (B, L, 2, H, 64) each row's
+// own tail, written at pos -> o (B, 1, H, 64).  Row b of group b / n attends prefix rows < prefix_len, tail rows < pos
+// and its new row.  The split partials' workspace is allocated here.
+Tensor attn_decode_prefix(const Tensor& qkv, const Tensor& prefix_kv, const Tensor& prefix_len, Tensor& kv,
+                          const Tensor& pos, double scale) {
+    const char* op = "attn_decode_prefix";
+    CHECK_CUDA(qkv); CHECK_BF16(qkv); CHECK_CUDA(prefix_kv); CHECK_BF16(prefix_kv); CHECK_CUDA(kv); CHECK_BF16(kv);
+    GUARD(qkv);
+    TORCH_CHECK(qkv.dim() == 5 && qkv.size(1) == 1 && qkv.size(2) == 3, op, ": qkv must be (B, 1, 3, H, D), got ",
+                qkv.sizes());
+    const int64_t B = qkv.size(0), H = qkv.size(3), D = qkv.size(4);
+    TORCH_CHECK(prefix_kv.dim() == 5 && prefix_kv.size(2) == 2 && prefix_kv.size(3) == H && prefix_kv.size(4) == D,
+                op, ": prefix_kv must be (G, P, 2, H, D) for qkv ", qkv.sizes(), ", got ", prefix_kv.sizes());
+    TORCH_CHECK(kv.dim() == 5 && kv.size(0) == B && kv.size(2) == 2 && kv.size(3) == H && kv.size(4) == D,
+                op, ": kv must be (B, L, 2, H, D) for qkv ", qkv.sizes(), ", got ", kv.sizes());
+    const int64_t G = prefix_kv.size(0), P = prefix_kv.size(1), L = kv.size(1);
+    TORCH_CHECK(G >= 1 && B >= 1 && B % G == 0, op, ": the batch ", B, " is not a multiple of the ", G, " prompts");
+    const int64_t n = B / G;
+    TORCH_CHECK(n <= 64, op, ": ", n, " samples per prompt (1..64)");
+    TORCH_CHECK(D == 64, op, ": head size ", D, " (64 only)");
+    TORCH_CHECK(P >= 1 && P <= 1024 && L >= 1 && L <= 1024, op, ": prefix length ", P, " / tail length ", L,
+                " outside 1..1024");
+    TORCH_CHECK(H >= 1 && B * H <= (int64_t)1 << 24, op, ": B * H out of range");
+    TORCH_CHECK(prefix_kv.device() == qkv.device() && kv.device() == qkv.device(), op,
+                ": qkv, prefix_kv and kv must be on one device");
+    check_index(op, "prefix_len", prefix_len, G, qkv.device());
+    check_index(op, "pos", pos, B, qkv.device());
+    const std::vector<long> q4 = strides_rows16(op, "qkv", qkv), ps = strides_rows16(op, "prefix_kv", prefix_kv),
+                            cs = strides_rows16(op, "kv", kv);
+    // the append writes through kv's strides: its rows must not overlap
+    TORCH_CHECK(kv.stride(3) >= D && kv.stride(2) >= H * kv.stride(3) && kv.stride(1) >= 2 * kv.stride(2) &&
+                    (B == 1 || kv.stride(0) >= L * kv.stride(1)),
+                op, ": kv must be a dense (B, L, 2, H, D) layout, got strides ", kv.strides());
+    Tensor o = at::empty({B, 1, H, D}, qkv.options());
+    Tensor ws = at::empty({rn_attn_prefix_ws_floats((int)G, (int)n, (int)H, (int)P)}, qkv.options().dtype(at::kFloat));
+    const long qs[3] = {q4[0], q4[2], q4[3]};
+    const int rc = rn_attn_decode_prefix(qkv.data_ptr(), prefix_kv.data_ptr(), prefix_len.data_ptr(),
+                                         prefix_len.scalar_type() == at::kLong ? 1 : 0, kv.data_ptr(), pos.data_ptr(),
+                                         pos.scalar_type() == at::kLong ? 1 : 0, ws.data_ptr<float>(), o.data_ptr(),
+                                         (int)G, (int)n, (int)H, (int)P, (int)L, (int)D, qs, ps.data(), cs.data(),
+                                         (float)scale, cur_stream());
+    TORCH_CHECK(rc == 0, op, ": unsupported shape n=", n, " D=", D, " P=", P, " L=", L);
+    return o;
 }
 
 // fused token sampler (sampling.hip): logits (B, V) bf16 / fp32 with a unit column stride and a row
@@ -460,6 +507,15 @@ TORCH_LIBRARY_FRAGMENT(replicann_kv8, m) {
 TORCH_LIBRARY_IMPL(replicann_kv8, CUDA, m) {
     m.impl("attn_decode", &attn_decode_kv8);
     m.impl("append", &kv8_append);
+}
+
+// n samples per prompt over a shared prompt cache: the same again
+TORCH_LIBRARY_FRAGMENT(replicann_prefix, m) {
+    m.def("attn_decode(Tensor qkv, Tensor prefix_kv, Tensor prefix_len, Tensor(a!) kv, Tensor pos, float scale) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(replicann_prefix, CUDA, m) {
+    m.impl("attn_decode", &attn_decode_prefix);
 }
 
 TORCH_LIBRARY_IMPL(replicann, CUDA, m) {

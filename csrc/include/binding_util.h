@@ -40,6 +40,30 @@ inline const uint64_t* seed_ptr(const optional<Tensor>& sb) {
     return (const uint64_t*)sb->data_ptr();
 }
 
+// a 5-D bf16 tensor whose head rows the kernels move as 16-byte vectors: an aligned base, a unit last stride and
+// every other stride a non-negative multiple of 8 elements; returns the first four strides
+inline std::vector<long> strides_rows16(const char* op, const char* what, const Tensor& t) {
+    TORCH_CHECK(t.dim() == 5, op, ": ", what, " must have 5 dimensions, got ", t.sizes());
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 && t.stride(4) == 1, op, ": ", what,
+                " needs a 16-byte aligned base and a contiguous head dimension");
+    std::vector<long> s;
+    for (int d = 0; d < 4; ++d) {
+        TORCH_CHECK(t.stride(d) % 8 == 0 && t.stride(d) >= 0, op, ": ", what, " strides must be multiples of 8 elements, got ",
+                    t.strides());
+        s.push_back(t.stride(d));
+    }
+    return s;
+}
+
+// n contiguous int32 / int64 values on `dev` (lengths, positions: the kernels clamp them)
+inline void check_index(const char* op, const char* what, const Tensor& t, int64_t n, const c10::Device& dev) {
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == n && t.is_contiguous(), op, ": ", what, " must be a contiguous (", n,
+                ",) tensor, got ", t.sizes());
+    TORCH_CHECK(t.scalar_type() == at::kInt || t.scalar_type() == at::kLong, op, ": ", what,
+                " must be int32 or int64, got ", t.scalar_type());
+    TORCH_CHECK(t.device() == dev, op, ": ", what, " must be on ", dev);
+}
+
 inline void strides_bth(const Tensor& t, std::vector<long>& s) {
     TORCH_CHECK(t.dim() == 4 && t.stride(3) == 1, "attention tensors must be (B, T, H, D) with unit D stride");
     s.push_back(t.stride(0)); s.push_back(t.stride(1)); s.push_back(t.stride(2));

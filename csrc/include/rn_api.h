@@ -237,6 +237,20 @@ int rn_attn_decode_kv8(const void* qkv, void* kv8, float* kv_scale, const void* 
 int rn_kv8_append(const void* kv_new, void* kv8, float* kv_scale, const void* pos, int pos64, int pos_n, int B, int T,
                   int H, int L, int D, const long* ns, const long* cs, hipStream_t st);
 
+// ------------------------------------------------------------------ attention_decode_prefix.hip
+// One-token attention for n samples per prompt over a shared prompt cache, the append folded in: qkv
+// (B = G n, 1, 3, H, 64) bf16 with the element strides qs (batch, q|k|v, head); prefix_kv (G, P <= 1024, 2, H, 64),
+// read only, strides ps (group, row, k|v, head); prefix_len G row counts (int64 if plen64 else int32, clamped to
+// [0, P] on the device); kv (B, L <= 1024, 2, H, 64) each row's own tail, strides cs (batch, row, k|v, head); pos B
+// write rows (int64 if pos64, clamped to [0, L]).  Row b = g n + s: the new K / V rows are written to kv[b, pos[b]] if
+// pos[b] < L and the query attends prefix rows < prefix_len[g], tail rows < pos[b] and the new row; o (B, 1, H, 64)
+// contiguous.  1 <= n <= 64.  ws: rn_attn_prefix_ws_floats(G, n, H, P) fp32 of workspace (the split partials).
+// Two launches.  Returns -1 for what it does not take.
+long rn_attn_prefix_ws_floats(int G, int n, int H, int P);
+int rn_attn_decode_prefix(const void* qkv, const void* prefix_kv, const void* prefix_len, int plen64, void* kv,
+                          const void* pos, int pos64, float* ws, void* o, int G, int n, int H, int P, int L, int D,
+                          const long* qs, const long* ps, const long* cs, float scale, hipStream_t st);
+
 // ------------------------------------------------------------------ sampling.hip
 // logits (B, V) bf16 / fp32 with row stride ld >= V; exactly one of u (B fp32 in [0, 1)) and seed
 // (row b draws hash_uniform(*seed, b)); params: 3 fp32 on the device (temperature, top_k, top_p)

@@ -7,6 +7,7 @@
     replicann generate --model gpt2-medium --draft-model gpt2-small --draft-k 4 --temperature 0
     replicann generate --model gpt2-medium --draft-model gpt2-small --temperature 0.8 --top-k 50 --sampler native
     replicann generate --model gpt2-small --batch-size 64 --prompt-len 896 --new 128 --kv-dtype fp8
+    replicann generate --model gpt2-small --prompt-len 896 --new 128 --num-samples 64
     replicann build            # compile the gfx950 extension in-tree (hipcc --offload-arch=gfx950)
     replicann <train args...>  # no command: train (kept for ``python -m replicann --model ...``)
 

@@ -127,6 +127,9 @@ class Attention(nn.Module):
             if cache.fp8:  # the cache quantises the new rows itself: append and attention are one call on the packed qkv
                 qkv = self.c_attn(h).view(B, T, 3, self.n_head, E // self.n_head)
                 return self.c_proj(cache.step8(layer, qkv, self.causal).reshape(B, T, E), residual=residual)
+            if cache.shared and cache.per_seq:  # n samples per prompt: the tail's append and the attention are one call
+                qkv = self.c_attn(h).view(B, T, 3, self.n_head, E // self.n_head)
+                return self.c_proj(cache.step_shared(layer, qkv).reshape(B, T, E), residual=residual)
             if cache.device_pos and T == 1 and self.c_attn.fp8_state is None:
                 # captured decode step: the projection's epilogue appends this token's key / value row
                 buf = cache.kv[layer]

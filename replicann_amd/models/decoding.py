@@ -46,13 +46,36 @@ class KVCache:
     a one-token step in any mode is one ``ops.attention_decode_kv8`` — append and attention — at the mode's own
     position tensor, which reads the rows below the position and nothing else, so device mode keeps no key
     mask; a prefill attends its own unquantised keys / values and stores them with ``ops.kv8_append``.  The
-    window step is not available on an fp8 cache."""
+    window step is not available on an fp8 cache.
 
-    def __init__(self, n_layer, max_len, kv_dtype=None):
+    ``samples=n`` (default 1: the cache above, untouched): n continuations per prompt over ONE copy of the
+    prompts' rows.  The states:
+      * prefill — an ordinary host-mode pass over the G prompts (uniform or right-padded ragged) whose buffers
+        ``prefix[layer]`` (G, max_len, 2, H, D) are read only from then on;
+      * ``to_per_sequence(lens)`` fans out: ``prefix_len`` (G,) = lens, and the per-sequence triple (``_rows``,
+        ``lens``, ``active``) gets B = G · n entries — row b is sample b % n of prompt b // n — with ``_rows`` = 0:
+        the position in the row's own TAIL ``kv[layer]`` (B, tail_len, 2, H, D), the keys / values of the tokens
+        the sample has generated;
+      * from then on it is a per-sequence-mode cache whose positions are tail positions (``begin_step`` /
+        ``end_step`` / ``active`` / ``snapshot`` / ``restore``; ``pos`` bounds them against ``tail_len``);
+        ``embed`` reads wpe[prefix_len[b // n] + _rows[b]] and the attention layer calls ``step_shared``: one
+        ``ops.attention_decode_prefix`` — the append to the tail and the attention over prefix, tail and new row.
+    The window step and ``kv_dtype="fp8"`` are not available with ``samples > 1``."""
+
+    def __init__(self, n_layer, max_len, kv_dtype=None, samples=1, tail_len=None):
         if kv_dtype not in (None, "fp8"):
             raise ValueError(f"kv_dtype must be None or 'fp8', got {kv_dtype!r}")
+        if not isinstance(samples, int) or isinstance(samples, bool) or samples < 1:
+            raise ValueError(f"samples must be an int >= 1, got {samples!r}")
+        if samples > 1 and kv_dtype is not None:
+            raise ValueError("a KV cache shared by several samples per prompt (samples > 1) has no fp8 form: kv_dtype "
+                             "must be None")
         self.max_len, self.pos, self.mode = max_len, 0, "host"
         self.kv_dtype = kv_dtype
+        self.samples = samples
+        self.tail_len = max_len if tail_len is None else tail_len  # samples > 1: rows of each sample's own tail
+        self.prefix = [None] * n_layer  # samples > 1: the prompts' rows (G, max_len, 2, H, D); kv holds the tails
+        self.prefix_len = self._prefix_rows = None  # samples > 1: (G,) prompt lengths; the same per batch row (B,)
         self.kv = [None] * n_layer
         self.kv_scale = [None] * n_layer  # fp8 only
         self._host_pos = None  # fp8 only: the host position as a 1-element device tensor (eager steps)
@@ -65,6 +88,7 @@ class KVCache:
         """The pass inside is the window step (``GPT2.decode_window``): ``embed`` reads T position rows
         per batch row and the attention layers call ``window`` instead of ``update`` / ``attend``."""
         self._need_per_seq("windowed")
+        self._no_window()
         self.in_window = True
         try:
             yield self
@@ -74,6 +98,7 @@ class KVCache:
     device_pos = property(lambda self: self.mode != "host")
     fp8 = property(lambda self: self.kv_dtype == "fp8")
     per_seq = property(lambda self: self.mode == "per_seq")
+    shared = property(lambda self: self.samples > 1)  # several samples per prompt over one copy of its rows
 
     @property
     def pos_t(self):
@@ -97,6 +122,8 @@ class KVCache:
         valid positions; what the prefill wrote at or past lens[b] is never read and is overwritten as
         the row grows.  The host ``pos`` becomes max(lens), which eager steps check against max_len."""
         lens = torch.as_tensor(lens, dtype=torch.long).reshape(-1)
+        if self.shared:
+            return self._fan_out(lens)
         self.pos = int(lens.max())
         lens = lens.to(self.kv[0].device)
         if self._rows is None or self._rows.shape != lens.shape:
@@ -105,6 +132,30 @@ class KVCache:
         torch.add(lens, 1, out=self.lens)
         self.active.fill_(1)
         self.mode = "per_seq"
+
+    def _fan_out(self, lens):
+        """``to_per_sequence`` of a cache with ``samples`` = n > 1: the G prompts' rows become the read-only
+        prefix and every prompt's n samples start their own tail at row 0.  The tails and the device tensors
+        are allocated once (until the number of prompts changes): a captured step reads them by address."""
+        pre, n = self.prefix[0], self.samples
+        G, B = lens.numel(), lens.numel() * n
+        if pre is None:
+            raise ValueError("a shared KV cache fans out after a host-mode pass over the prompts (a prefill)")
+        if pre.shape[0] != G:
+            raise ValueError(f"the prefill wrote {pre.shape[0]} prompts, lens holds {G}")
+        lens = lens.to(pre.device)
+        if self.prefix_len is None or self.prefix_len.shape != lens.shape:
+            self.prefix_len = torch.empty_like(lens)
+            self._prefix_rows, self._rows, self.lens, self.active = (
+                torch.empty(B, dtype=torch.long, device=pre.device) for _ in range(4))
+            # zeroed like the prefix: rows at or past a position are never read, but should not look like data
+            self.kv = [p.new_zeros(B, self.tail_len, *p.shape[2:]) for p in self.prefix]
+        self.prefix_len.copy_(lens)
+        self._prefix_rows.copy_(lens.repeat_interleave(n))
+        self._rows.zero_()
+        self.lens.fill_(1)
+        self.active.fill_(1)
+        self.pos, self.mode = 0, "per_seq"  # pos: the host bound of the TAIL positions from here on
 
     def reset(self):
         """Start a new sequence in the same buffers (host mode, position 0)."""
@@ -135,6 +186,9 @@ class KVCache:
                 raise ValueError("an fp8 cache in device mode takes one token per step")
         elif self.mode == "per_seq" and T != 1:
             raise ValueError("a cache in per-sequence mode takes one token per row and step")
+        elif self.shared and self.mode == "per_seq":
+            if self.pos + T > self.tail_len:
+                raise ValueError(f"KV cache full: {self.pos} + {T} tail rows > {self.tail_len}")
         elif self.pos + T > self.max_len:
             raise ValueError(f"KV cache full: {self.pos} + {T} > {self.max_len}")
 
@@ -153,11 +207,17 @@ class KVCache:
         if self.mode != "per_seq":
             raise ValueError(f"KVCache.{what} needs a cache in per-sequence mode (a ragged prefill)")
 
+    def _no_window(self):
+        if self.shared:
+            raise ValueError("the window step is not available on a KV cache shared by several samples per prompt "
+                             "(samples > 1)")
+
     def window(self, layer, qkv):
         """Append the key / value rows of ``qkv`` (B, T, 3, H, D) at each row's position and attend its T
         queries to the cached rows and the window so far: one ``ops.attention_window``.  The position
         does not move (``advance``): whatever the window wrote past it stays unread."""
         self._need_per_seq("window")
+        self._no_window()
         if self.fp8:
             raise ValueError("the window step is not available on an fp8 KV cache")
         return ops.attention_window(qkv, self.kv[layer], self._rows)
@@ -191,6 +251,9 @@ class KVCache:
             return ops.embedding(idx.reshape(1, -1), wte, wpe.index_select(0, at.view(-1))).view(B, T, -1)
         if self.mode == "host":
             return ops.embedding(idx, wte, wpe[self.pos: self.pos + idx.shape[1]])
+        if self.shared:  # a sample's position is its prompt's length plus its tail position, clamped to the table
+            at = (self._prefix_rows + self._rows).clamp_(0, wpe.shape[0] - 1)
+            return ops.embedding(idx.view(1, -1), wte, wpe.index_select(0, at)).view(idx.shape[0], 1, -1)
         rows = wpe.index_select(0, self.pos_t)
         if self.mode == "device":
             return ops.embedding(idx, wte, rows)
@@ -201,14 +264,15 @@ class KVCache:
         """Append ``kv`` (B, T, 2, H, D) — the key / value slice of the packed QKV projection — at
         the cache position; returns the (key, value) views the attention reads.  K and V share one
         buffer per layer, so an append is ONE copy (slice copy_ / index_copy_ / scatter_ by mode)."""
-        buf = self.kv[layer]
+        store = self.prefix if self.shared else self.kv  # a shared cache's host-mode passes write the prompts' rows
+        buf = store[layer]
         if self.mode == "host":
             B, T, _, H, D = kv.shape
             if buf is None:
                 # zeroed, not empty: the device-mode step reads the WHOLE buffer under the key mask, and
                 # a masked row still enters P·V as 0 · v — a NaN bit pattern in an unwritten row would
                 # turn that into NaN
-                buf = self.kv[layer] = kv.new_zeros(B, self.max_len, 2, H, D)
+                buf = store[layer] = kv.new_zeros(B, self.max_len, 2, H, D)
             buf[:, self.pos: self.pos + T].copy_(kv)
             return buf[:, : self.pos + T, 0], buf[:, : self.pos + T, 1]
         if self.mode == "device":
@@ -218,6 +282,16 @@ class KVCache:
                 raise ValueError("KV cache in per-sequence mode appends one token per step")
             buf.scatter_(1, self._rows.view(-1, 1, 1, 1, 1).expand_as(kv), kv)
         return buf[:, :, 0], buf[:, :, 1]
+
+    def step_shared(self, layer, qkv):
+        """The one-token step of a cache with ``samples > 1`` after the fan-out: ``qkv`` (B, 1, 3, H, D), the packed
+        projection output -> (B, 1, H, D).  One ``ops.attention_decode_prefix``: row b's new key / value row is
+        written to its tail at ``_rows[b]`` and its query attends its prompt's ``prefix_len[b // n]`` rows, its own
+        tail rows below ``_rows[b]`` and the new row."""
+        self._need_per_seq("step_shared")
+        if qkv.shape[1] != 1:
+            raise ValueError("a KV cache shared by several samples per prompt takes one token per row and step")
+        return ops.attention_decode_prefix(qkv, self.prefix[layer], self.prefix_len, self.kv[layer], self._rows)
 
     def step8(self, layer, qkv, causal):
         """An fp8 cache's append and attention in one: ``qkv`` (B, T, 3, H, D), the packed projection output,
@@ -303,12 +377,15 @@ class _GraphRegistry(dict):
     (batch, cache length, dtype, device, parameter storage[, "ragged" for the per-sequence step]
     [, "sampler" for a step captured together with the native sampler][, "window", T for the window step of
     T tokens per row: its output is the greedy ids (B, T)][, "logits" for the window step whose output is the
-    logits (B, T, vocab) instead][, "fp8" for a step over an fp8 KV cache, always last]) → (cache, graph, token buffer, logits), so a serving loop captures once per (batch, length bucket).  A sampler entry holds the
+    logits (B, T, vocab) instead][, "fp8" for a step over an fp8 KV cache, always last][, "prompts", G, "tail", tail length, "samples", n for the
+    step of n samples per prompt over a shared prompt cache, always last: batch is then G · n and cache length the
+    prompts' bucket, so the key holds everything its buffers' shapes depend on and a shared step never aliases a
+    plain one]) → (cache, graph, token buffer, logits), so a serving loop captures once per (batch, length bucket).  A sampler entry holds the
     sampled tokens (B, 1) in place of the logits, then the device tensor its settings are read from:
     one graph whatever the temperature / top_k / top_p.
     At most DECODE_GRAPHS_MAX (REPLICANN_DECODE_GRAPHS, default 4) are kept; each holds its KV cache."""
 
-    def lookup(self, model, B, L, ragged, use, sampler=False, window=None, logits=False, kv_dtype=None):
+    def lookup(self, model, B, L, ragged, use, sampler=False, window=None, logits=False, kv_dtype=None, shared=None):
         """(key, its stored entry — now the most recently used — or None).  The parameters' storage
         is part of the key: a graph reads them by address, so entries captured before a parameter was
         re-assigned (p.data = ...) are dropped here, whether or not this call will ``use`` a graph."""
@@ -318,6 +395,8 @@ class _GraphRegistry(dict):
         key += ("window", window) if window else ()  # the captured window step of this many tokens per row
         key += ("logits",) if logits else ()  # ... returning its logits, not the greedy ids
         key += (kv_dtype,) if kv_dtype else ()  # an fp8 cache's step never aliases the bf16 one
+        # shared = (tail length, n): n samples per prompt over one copy of the B // n prompts' rows
+        key += ("prompts", B // shared[1], "tail", shared[0], "samples", shared[1]) if shared else ()
         for k in [k for k in self if k[4] != sig]:
             del self[k]
         entry = self.pop(key, None) if use else None
@@ -586,18 +665,30 @@ class _StepDriver:
     """One ``generate`` call's cache and one-token step.  With ``graph``, an earlier call's cache and
     captured step of the same key are reused; failing that the first ``step`` captures (and stores) one."""
 
-    def __init__(self, model, B, length, ragged, graph, sampling, native, kv_dtype=None):
+    def __init__(self, model, B, length, ragged, graph, sampling, native, kv_dtype=None, samples=1, new=None):
         c = model.config
-        if graph or ragged:  # one captured step (and cache) serves every length of a bucket
-            length = min(c.block_size, -(-length // DECODE_LEN_BUCKET) * DECODE_LEN_BUCKET)
+
+        def bucket(x):
+            return min(c.block_size, -(-x // DECODE_LEN_BUCKET) * DECODE_LEN_BUCKET)
+
+        shared = None
+        if samples > 1:  # B = G · samples rows; length: the longest prompt; new: the new-token budget (the tails)
+            length, shared = bucket(length), (bucket(new), samples)
+        elif graph or ragged:  # one captured step (and cache) serves every length of a bucket
+            length = bucket(length)
         self.model, self.B, self.graph, self.graphs = model, B, graph, registry(model)
         # sampling: (temperature, top_k, generator, top_p); native: ops.sample_logits instead of _sample
         self.sampling, self.native = sampling, native
         self.fused = native and graph  # the sampler is part of the captured step
         self.settings_sent = False  # fused: has this call written its settings into the graph's tensor?
         self.key, self.entry = self.graphs.lookup(model, B, length, ragged, graph, sampler=self.fused,
-                                                  kv_dtype=kv_dtype)
-        self.cache = KVCache(c.n_layer, length, kv_dtype) if self.entry is None else self.entry[0]
+                                                  kv_dtype=kv_dtype, shared=shared)
+        if self.entry is not None:
+            self.cache = self.entry[0]
+        elif shared:
+            self.cache = KVCache(c.n_layer, length, samples=samples, tail_len=shared[0])
+        else:
+            self.cache = KVCache(c.n_layer, length, kv_dtype)
         self.cache.reset()
 
     def step(self, tok):
@@ -639,7 +730,7 @@ class _StepDriver:
 @torch.no_grad()
 def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=None, generator=None, graph=None,
              prompt_lens=None, eos_token_id=None, pad_token_id=None, sampler="torch", draft=None, draft_k=4,
-             stats=None, kv_dtype=None):
+             stats=None, kv_dtype=None, num_samples=1):
     """Autoregressive sampling with a KV cache: ``idx`` (B, T0) prompt → (B, T0 + max_new_tokens).
     ``temperature`` 0 = greedy; ``top_k`` / ``top_p`` restrict sampling.  One prefill pass over the prompt, then one-token steps whose
     attention reads the cached keys / values (no recomputation of the prefix).  ``graph``
@@ -685,7 +776,24 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     with one power-of-two scale per 64-element head row (``decoding.KVCache``, ``ops.kv8``) — 0.53 of the
     bytes, in memory and per step — and the one-token step's attention quantises and appends the new row
     itself (``ops.attention_decode_kv8``).  The prefill attends its own unquantised keys / values.  Every mode
-    above works with it except ``draft``, which raises: the window step has no fp8 form."""
+    above works with it except ``draft``, which raises: the window step has no fp8 form.
+
+    ``num_samples=n`` (default 1: everything above, unchanged): n continuations of every prompt — ``idx`` is
+    (G, T0) and the result has G · n rows, row g · n + s being sample s of prompt g (with ``prompt_lens`` /
+    ``eos_token_id``: ``(tokens, lens)`` over G · n rows).  The prompts are prefilled ONCE, at batch G; the last
+    position's logits are repeated n times and every sample draws its own first token with the call's sampler;
+    the one-token steps then run at batch G · n over a cache that keeps one copy of each prompt's rows and a
+    short tail per sample (``decoding.KVCache(samples=n)``, ``ops.attention_decode_prefix``): the prompt's keys /
+    values are stored once and read once per step, not n times.  Uniform or ragged prompts, EOS (rows finish
+    independently), eager or captured steps and both samplers work with it; ``draft`` and ``kv_dtype`` raise."""
+    if not isinstance(num_samples, int) or isinstance(num_samples, bool) or num_samples < 1:
+        raise ValueError(f"num_samples must be an int >= 1, got {num_samples!r}")
+    if num_samples > 1 and draft is not None:
+        raise ValueError("generate(num_samples > 1) with draft= is not supported: speculative decoding over a shared "
+                         "prompt cache needs a window step it does not have")
+    if num_samples > 1 and kv_dtype is not None:
+        raise ValueError("generate(num_samples > 1) with kv_dtype= is not supported: the shared prompt cache has no "
+                         "fp8 form")
     B, T0 = idx.shape
     ragged = prompt_lens is not None or eos_token_id is not None
     if top_p is not None and not 0.0 < top_p <= 1.0:
@@ -705,7 +813,7 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
         raise ValueError(f"sampler='native' needs temperature >= 0 and top_k >= 0, got {temperature}, {top_k}")
     plens = [T0] * B if prompt_lens is None else host_lens("prompt_lens", prompt_lens, B, T0)
     Tm = max(plens)
-    if ragged and max_new_tokens < 1:
+    if (ragged or num_samples > 1) and max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
     if Tm + max_new_tokens > model.config.block_size:
         raise ValueError(f"prompt {Tm} + {max_new_tokens} new tokens exceeds block_size {model.config.block_size}")
@@ -727,6 +835,11 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
     was_training = model.training
     model.eval()
     try:
+        if num_samples > 1:  # one prefill at batch B, then the ragged loop over B · num_samples rows
+            driver = _StepDriver(model, B * num_samples, Tm, True, use_graph, (temperature, top_k, generator, top_p),
+                                 native, samples=num_samples, new=max_new_tokens)
+            out = _ragged_loop(driver, idx[:, :Tm], plens, max_new_tokens, eos_token_id, pad_token_id, num_samples)
+            return out if ragged else out[0]  # no EOS, equal lengths: every row is full
         driver = _StepDriver(model, B, Tm + max_new_tokens, ragged, use_graph,
                              (temperature, top_k, generator, top_p), native, kv_dtype)
         if ragged:
@@ -742,7 +855,11 @@ def generate(model, idx, max_new_tokens, *, temperature=1.0, top_k=None, top_p=N
         model.train(was_training)
 
 
-def _ragged_loop(driver, idx, plens, max_new_tokens, eos, pad):
+def _ragged_loop(driver, idx, plens, max_new_tokens, eos, pad, samples=1):
+    logits = driver.model.decode_step(idx, driver.cache, lens=plens)
+    if samples > 1:  # the one prefill serves every sample of a prompt: each draws its own first token
+        idx, logits = idx.repeat_interleave(samples, 0), logits.repeat_interleave(samples, 0)
+        plens = [n for n in plens for _ in range(samples)]
     (B, Tm), dev = idx.shape, idx.device  # idx: the prompts cut to the longest one
     if pad is None:
         pad = eos if eos is not None else 0
@@ -752,7 +869,6 @@ def _ragged_loop(driver, idx, plens, max_new_tokens, eos, pad):
     keep = torch.arange(Tm, device=dev).unsqueeze(0) < lens.unsqueeze(1)
     tokens[:, :Tm] = torch.where(keep, idx, tokens[:, :Tm])
     finished = torch.zeros(B, dtype=torch.bool, device=dev)
-    logits = driver.model.decode_step(idx, driver.cache, lens=plens)
     for i in range(max_new_tokens):
         nxt = driver.pick(logits)
         nxt = torch.where(finished.unsqueeze(1), torch.full_like(nxt, pad), nxt)  # finished rows emit pad
@@ -771,7 +887,8 @@ def _ragged_loop(driver, idx, plens, max_new_tokens, eos, pad):
 
 def generate_batch(model, prompts, max_new_tokens, **kw):
     """``generate`` for a list of 1-D token tensors of any lengths: pads them, runs the ragged
-    path and returns a list of 1-D tensors ``prompt_b ‖ generated_b``, each trimmed to its length."""
+    path and returns a list of 1-D tensors ``prompt_b ‖ generated_b``, each trimmed to its length.
+    With ``num_samples=n`` the list holds n tensors per prompt, prompt by prompt."""
     plens = [int(p.numel()) for p in prompts]
     if not plens or min(plens) < 1:
         raise ValueError("generate_batch needs at least one prompt, each of at least one token")

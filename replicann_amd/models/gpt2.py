@@ -185,7 +185,9 @@ class GPT2(nn.Module):
         if lens is not None:
             cache.to_per_sequence(lens)
             # each row's own last valid position, gathered BEFORE the LM head: the head runs on B rows
-            last = h[torch.arange(B, device=h.device), cache.pos_t - 1].unsqueeze(1).contiguous()
+            # (a cache shared by several samples per prompt has fanned out: its B rows' lengths are prefix_len)
+            ends = cache.prefix_len if cache.shared else cache.pos_t
+            last = h[torch.arange(B, device=h.device), ends - 1].unsqueeze(1).contiguous()
             return ops.linear(last, self.wte)[:, 0, : self.config.vocab_size]
         logits = ops.linear(h[:, -1:].contiguous(), self.wte)[:, 0, : self.config.vocab_size]
         cache.end_step(T)

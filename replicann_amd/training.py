@@ -493,7 +493,8 @@ def generate_main(argv=None):
     checkpoint written by ``train(checkpoint=...)`` — with the KV cache and the hipGraph-replayed
     decode step (``GPT2.generate``).  Prints one JSON line: the token ids, decode timing.  ``--prompt``
     may be repeated (one sequence each, of any lengths) and ``--eos`` stops a sequence at that token:
-    the line then carries each sequence's generated tokens and total length."""
+    the line then carries each sequence's generated tokens and total length.  ``--num-samples n``: n
+    continuations per prompt over one shared copy of its KV rows, printed as one list of n per prompt."""
     ap = argparse.ArgumentParser(description="replicann generation entrypoint (GPT-2 models)")
     ap.add_argument("--model", default="gpt2-small")
     ap.add_argument("--checkpoint", default=None)
@@ -521,6 +522,9 @@ def generate_main(argv=None):
     ap.add_argument("--kv-dtype", choices=("fp8",), default=None,
                     help="fp8: keep the KV cache as e4m3 bytes with one scale per head row (about half the bytes; not "
                          "with --draft-model)")
+    ap.add_argument("--num-samples", type=int, default=1,
+                    help="continuations per prompt over one shared copy of the prompt's KV rows; the output is grouped "
+                         "by prompt (not with --draft-model or --kv-dtype)")
     a = ap.parse_args(argv)
     if not a.model.startswith("gpt2") or not (a.draft_model or "gpt2").startswith("gpt2"):
         raise SystemExit(f"generate: {a.model} / {a.draft_model} is not an autoregressive GPT-2 model")
@@ -547,6 +551,13 @@ def generate_main(argv=None):
         spec = dict(draft=draft, draft_k=a.draft_k, stats=stats)
     if a.kv_dtype:
         spec["kv_dtype"] = a.kv_dtype
+    n = a.num_samples
+    if n != 1:
+        spec["num_samples"] = n
+
+    def grouped(rows):
+        """With --num-samples n: one list of n rows per prompt."""
+        return rows if n == 1 else [rows[g:g + n] for g in range(0, len(rows), n)]
     gen = torch.Generator(device=dev).manual_seed(a.seed)
     if a.sampler == "native" and dev.type == "cuda":  # the device seed stream takes the generator's place
         from .ops import rng
@@ -565,9 +576,9 @@ def generate_main(argv=None):
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
-        new = [r[len(p):].tolist() for r, p in zip(rows, prompts)]
-        res = {"model": a.model, "tokens": new, "prompt_lens": [len(p) for p in prompts],
-               "lengths": [int(r.numel()) for r in rows], "new_tokens": a.new, "seconds": round(dt, 4),
+        new = [r[len(prompts[b // n]):].tolist() for b, r in enumerate(rows)]
+        res = {"model": a.model, "tokens": grouped(new), "prompt_lens": [len(p) for p in prompts],
+               "lengths": grouped([int(r.numel()) for r in rows]), "new_tokens": a.new, "seconds": round(dt, 4),
                "tokens_per_s": round(sum(map(len, new)) / dt, 1), **_spec_report(stats)}
         print(json.dumps(res))
         return res
@@ -581,7 +592,7 @@ def generate_main(argv=None):
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
-    res = {"model": a.model, "tokens": out[:, ids.shape[1]:].tolist(), "prompt_len": ids.shape[1],
+    res = {"model": a.model, "tokens": grouped(out[:, ids.shape[1]:].tolist()), "prompt_len": ids.shape[1],
            "new_tokens": a.new, "seconds": round(dt, 4), "tokens_per_s": round(out.shape[0] * a.new / dt, 1),
            **_spec_report(stats)}
     print(json.dumps(res))

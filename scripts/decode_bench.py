@@ -51,6 +51,16 @@ that the rows come from memory as in the step) and the two QKV projections alone
 
     python scripts/decode_bench.py --kv-fp8 --out profiles/decode_kv_fp8.txt
     rocprofv3 --kernel-trace --stats ... -- python scripts/decode_bench.py --kv-fp8 --prompts 896 --new 32   # per-kernel times
+
+``--samples``: n samples per prompt over one shared prompt cache (``generate(num_samples=n)``) against the captured
+ragged step on the repeated prompts (``generate(idx.repeat_interleave(n, 0), prompt_lens=...)``), GPT-2-small, 64 rows
+per step as G x n = 1 x 64, 4 x 16 and 16 x 4, 128 new tokens after prompts of 128 and of 896 tokens.  The protocol
+of ``--kv-fp8``: per case the two graphs alternated in one process after a warm-up of each, three rounds of 128
+replays, medians and the spread of the rounds; then the prefill of G prompts against G · n, each cache's bytes, the
+two criteria (1 x 64 at prompt 896: shared faster by more than the spread; prompt 128: every case at most 1.05x) and,
+inside captured graphs that walk the 12 layers' caches, the attention of each step alone.
+
+    python scripts/decode_bench.py --samples --out profiles/decode_shared_prefix.txt
 """
 
 import argparse
@@ -293,11 +303,12 @@ def kv_fp8(m, model, out_path, B=64, prompts=(128, 896), new=128, rounds=3):
             m.decode_step(idx, c)
             m.decode_step(idx[:, :1], c)  # tunes the one-token GEMM shapes outside the capture
             c.pos = prompt  # (the row that step wrote is overwritten by the first replay)
-            graphs[name] = (decoding.capture_step(m, c, B)[0], c)
+            cap = decoding.capture_step(m, c, B)
+            graphs[name] = (cap[0], c, cap)  # the graph reads its token buffer by address: kept alive beside it
             nbytes[name] = sum(t.numel() * t.element_size() for t in c.kv + (c.kv_scale if kvd else []))
         ms = {k: [] for k in graphs}
         for r in range(rounds):
-            for k, (g, c) in graphs.items():
+            for k, (g, c, _) in graphs.items():
                 snap = c.snapshot()
                 g.replay()
                 ms[k].append(_replay_ms(g, new - 1))  # rows prompt .. prompt + new - 1
@@ -357,6 +368,107 @@ def kv_fp8(m, model, out_path, B=64, prompts=(128, 896), new=128, rounds=3):
         errs.append(float((y - x).norm() / x.norm()))
     emit({"tiny model (random init), logits with the fp8 cache against the bf16 cache, relative L2": "not gated",
           "prefill": round(errs[0], 5), "steps": [round(e, 5) for e in errs[1:]], "max": round(max(errs[1:]), 5)})
+
+
+def shared_prefix(m, model, out_path, shapes=((1, 64), (4, 16), (16, 4)), prompts=(128, 896), new=128, rounds=3):
+    """n samples per prompt over one shared prompt cache against the captured ragged step on the repeated prompts
+    (``--samples``)."""
+    from replicann_amd import ops
+    from replicann_amd.models import decoding
+    from replicann_amd.models.decoding import KVCache
+    dev = torch.device("cuda")
+    sink = open(out_path, "a") if out_path else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+
+    def bucket(x):
+        return min(m.config.block_size, -(-x // decoding.DECODE_LEN_BUCKET) * decoding.DECODE_LEN_BUCKET)
+
+    emit({"bench": "n samples per prompt over a shared prompt cache", "model": model, "new_tokens": new, "dtype": "bf16",
+          "weights": "random init", "rounds": rounds, "replays_per_timing": new - 1})
+    nl, H = m.config.n_layer, m.config.n_head
+    for prompt in prompts:
+        for G, n in shapes:
+            B = G * n
+            idx = torch.randint(0, m.config.vocab_size, (G, prompt), device=dev)
+            rep = idx.repeat_interleave(n, 0)
+            tok = torch.randint(0, m.config.vocab_size, (B, 1), device=dev)
+            makers = {
+                "repeated prompts": (lambda: KVCache(nl, bucket(prompt + new)), rep, B),
+                "shared prompt": (lambda: KVCache(nl, bucket(prompt), samples=n, tail_len=bucket(new)), idx, G),
+            }
+            graphs, nbytes, prefill = {}, {}, {}
+            for name, (make, ids, rows) in makers.items():
+                c = make()
+                m.decode_step(ids, c, lens=[prompt] * rows)
+                snap = c.snapshot()
+                m.decode_step(tok, c)  # tunes the one-token GEMM shapes outside the capture
+                c.restore(snap)
+                cap = decoding.capture_step(m, c, B)
+                cap[1].copy_(tok)
+                # (the graph reads its token buffer by address: the whole capture is kept alive beside it)
+                graphs[name] = (cap[0], c, cap)
+                nbytes[name] = sum(t.numel() * t.element_size() for t in c.kv + [p for p in c.prefix if p is not None])
+                prefill[name] = min(_timed(lambda: m.decode_step(ids, make(), lens=[prompt] * rows))[0] for _ in range(2))
+            ms = {k: [] for k in graphs}
+            for r in range(rounds):
+                for k, (g, c, _) in graphs.items():
+                    snap = c.snapshot()
+                    g.replay()
+                    ms[k].append(_replay_ms(g, new - 1))  # rows prompt .. prompt + new - 1 / tail rows 0 .. new - 1
+                    c.restore(snap)
+                    emit({"prompt": prompt, "G x n": f"{G} x {n}", "case": k, "round": r,
+                          "ms_per_step": round(ms[k][-1], 4)})
+            med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+            spread = max(max(v) - min(v) for v in ms.values())
+            a, b = "repeated prompts", "shared prompt"
+            rec = {"summary": "median ms per captured step", "prompt": prompt, "G x n": f"{G} x {n}",
+                   **{k: round(v, 4) for k, v in med.items()}, "spread of the rounds ms": round(spread, 4),
+                   "shared_over_repeated": round(med[b] / med[a], 4),
+                   **{f"{k} prefill ms": round(v * 1e3, 3) for k, v in prefill.items()},
+                   **{f"{k} cache bytes": v for k, v in nbytes.items()},
+                   "cache bytes shared_over_repeated": round(nbytes[b] / nbytes[a], 4)}
+            if prompt >= 512 and (G, n) == (1, 64):
+                rec["criterion: shared faster by more than the spread"] = bool(med[a] - med[b] > spread)
+            if prompt < 512:
+                rec["criterion: shared at most 1.05x"] = bool(med[b] <= 1.05 * med[a])
+            emit(rec)
+            # the kernels alone, half-way through the generation (new / 2 tail rows): consecutive calls walk the 12
+            # layers' caches, as the step does, so that no call finds its rows in the last-level cache
+            cs, cb = graphs[b][1], graphs[a][1]
+            turn = [0]
+
+            def layer():
+                turn[0] = (turn[0] + 1) % nl
+                return turn[0]
+            plen = torch.full((G,), prompt, device=dev)
+            none = torch.zeros_like(plen)
+            pos = torch.full((B,), new // 2, device=dev)
+            lens = torch.full((B,), prompt + new // 2 + 1, device=dev)
+            with torch.no_grad():
+                qkv = torch.randn(B, 1, 3, H, 64, device=dev).bfloat16()
+
+                def plain_attn():
+                    kv = cb.kv[layer()]
+                    return ops.attention_decode(qkv[:, :, 0], kv[:, :, 0], kv[:, :, 1], lens=lens)
+
+                def shared_attn(pl=plen):
+                    i = layer()
+                    return ops.attention_decode_prefix(qkv, cs.prefix[i], pl, cs.kv[i], pos)
+
+                emit({"prompt": prompt, "G x n": f"{G} x {n}",
+                      "us per call inside a captured graph": "24 calls over the 12 layers' caches, new / 2 rows generated",
+                      "attn_decode64_k (repeated prompts, lens)": round(_op_us(plain_attn, calls=2 * nl), 2),
+                      "prefix_partials64_k + prefix_tail_merge64_k (shared prompt, append included)":
+                          round(_op_us(shared_attn, calls=2 * nl), 2),
+                      "the same at prefix_len 0 (the partials launch returns at once: the tail + merge launch and the "
+                      "boundary)": round(_op_us(lambda: shared_attn(none), calls=2 * nl), 2)})
+            del graphs, cs, cb
 
 
 def _composed_verify(tl, dl, drafts, temperature, top_k, top_p, u):
@@ -474,7 +586,10 @@ def main():
     ap.add_argument("--sample", action="store_true", help="sampler='torch' against sampler='native' (see above)")
     ap.add_argument("--speculative", action="store_true", help="the cost of a speculative round (see above)")
     ap.add_argument("--kv-fp8", action="store_true", help="the captured step over an fp8 KV cache against the bf16 one (see above)")
-    ap.add_argument("--prompts", default="128,896", help="--kv-fp8: the prompt lengths (one alone for a kernel trace)")
+    ap.add_argument("--samples", action="store_true",
+                    help="n samples per prompt over a shared prompt cache against the repeated prompts (see above)")
+    ap.add_argument("--prompts", default="128,896",
+                    help="--kv-fp8, --samples: the prompt lengths (one alone for a kernel trace)")
     ap.add_argument("--draft-model", default="gpt2-small")
     ap.add_argument("--out", default="", help="--speculative, --kv-fp8: also append every line to this file")
     ap.add_argument("--temperature", type=float, default=0.0,
@@ -512,6 +627,9 @@ def main():
     if a.kv_fp8:
         with torch.no_grad():
             return kv_fp8(m, a.model, a.out, prompts=[int(p) for p in a.prompts.split(",")], new=a.new)
+    if a.samples:
+        with torch.no_grad():
+            return shared_prefix(m, a.model, a.out, prompts=[int(p) for p in a.prompts.split(",")], new=a.new)
     if a.ragged:
         return ragged(m, a.model, prompt=a.prompt, new=a.new)
     if a.sample:
